@@ -11,7 +11,14 @@ HBM before the timed region.  Multi-GPU: one process per GPU, the batch is
 sharded (each rank owns its own 65536 polynomials: weak scaling), no
 collective in the data path; barrier + max-over-ranks timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps of C3 and prints the result line
+(value, ms_per_step, the HBM roofline of the timed kernel).  --full adds
+everything else beside it: the oracle spot checks, C4, the 62-bit prime, the
+negacyclic mode, the ciphertext-level side metrics, the host-resident path,
+the multi-GPU gather and the CPU baselines.  --dump-outputs DIR writes what
+the last timed step computed (a fixed sample of its rows) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -41,20 +48,30 @@ def parse():
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--batch", type=int, default=65536, help="polynomials per GPU")
     ap.add_argument("--q", type=int, default=P27)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (oracle spot checks, C4 polymul, 62-bit prime, "
+                         "negacyclic, ciphertext ops, host-resident path, gather, CPU baselines); the --q62/--no-*/"
+                         "--cpu-seconds switches below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the rows the last timed step "
+                         "computed to DIR/<name>.npy (float64)")
     ap.add_argument("--q62", action="store_true", help="also measure the 62-bit prime")
     ap.add_argument("--no-q62", dest="q62", action="store_false")
     ap.set_defaults(q62=True)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--mode", default="compat", choices=["compat", "negacyclic"],
-                    help="transform of the --only profiling runs (the default run reports both)")
+                    help="transform of the --only profiling runs and of the plain run (--full reports both)")
     ap.add_argument("--only", default="", help="run only this kernel (fwd_mul|polymul|fwd|inv) for profiling")
     ap.add_argument("--no-check", action="store_true", help="skip the oracle spot check (profiling runs)")
     ap.add_argument("--no-host", action="store_true", help="skip the host-resident (FHE_HOST, PCIe) measurement")
     ap.add_argument("--only-host", action="store_true", help="only the host-resident measurement (lab)")
     ap.add_argument("--no-cipher", dest="cipher", action="store_false",
                     help="skip the ciphertext-level side metrics (ct multiply, relinearize, blind rotate)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -141,7 +158,45 @@ def timed(dist, fn, steps, warmup):
     return max_over_ranks(dist, wall), max_over_ranks(dist, kernel_ms)
 
 
-def gpu_workload(fhe_gpu, n, q, batch, steps, warmup, dist, only="", check=True, mode="compat"):
+DUMP_BYTES = 32 << 20  # --dump-outputs: float64 bytes written per run (the limit is 64 MB)
+
+
+def dump_sample(batch, n, q):
+    """Row indices --dump-outputs writes: every row while they fit in
+    DUMP_BYTES, else a fixed seeded sample (the same from run to run)."""
+    parts = 1 if q <= (1 << 53) else 2
+    k = max(1, min(batch, DUMP_BYTES // (8 * n * parts)))
+    return np.sort(np.random.default_rng(20240607).choice(batch, size=k, replace=False))
+
+
+def dump_rows(dirname, name, out, q):
+    """--dump-outputs: the dump_sample() rows of `out` (the buffer the timed
+    launches of kernel `name` wrote, read after the last timed step) as
+    DIR/<name>.npy in float64.  Residues below 2^53 are exact in float64; a
+    wider modulus is written as its low and high 32-bit halves
+    (<name>_lo32.npy, <name>_hi32.npy)."""
+    parts = 1 if q <= (1 << 53) else 2
+    rows = dump_sample(out.shape[0], out.shape[1], q)
+    if out.is_cuda:
+        torch.cuda.synchronize()
+    got = out[torch.from_numpy(rows).to(out.device)].cpu().numpy().view(np.uint64)
+    os.makedirs(dirname, exist_ok=True)
+    if parts == 1:
+        np.save(os.path.join(dirname, f"{name}.npy"), got.astype(np.float64))
+    else:
+        np.save(os.path.join(dirname, f"{name}_lo32.npy"), (got & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}_hi32.npy"), (got >> np.uint64(32)).astype(np.float64))
+
+
+def gpu_workload(fhe_gpu, n, q, batch, steps, warmup, dist, only="", check=True, mode="compat", gather=True,
+                 dump=None):
+    """Times the kernels `only` selects ("" = C3 fwd_mul, the gather, C4
+    polymul).  dump = (DIR, kernel): after that kernel's timed steps, write
+    its output rows (dump_rows) before anything else reuses the buffer."""
+    def dump_after(kind):
+        if dump is not None and dump[1] == kind:
+            dump_rows(dump[0], kind, out, q)
+
     ring = fhe_gpu.PolynomialRing(n, q, mode=mode, device=torch.cuda.current_device())
     g = torch.Generator(device="cuda").manual_seed(1234 + int(os.environ.get("RANK", "0")))
     a = torch.randint(0, q, (batch, n), device="cuda", dtype=torch.int64, generator=g)
@@ -153,18 +208,22 @@ def gpu_workload(fhe_gpu, n, q, batch, steps, warmup, dist, only="", check=True,
     # timed launches wrote, bit-exact vs the oracle (outside timing)
     if only in ("", "fwd_mul"):
         res["fwd_mul"] = timed(dist, lambda: ring.forward_ntt_mul(a, b, out=out), steps, warmup)
+        dump_after("fwd_mul")
         if check and mode == "compat":
             checks.append(_check_rows("fwd_mul", a, b, out, n, q))
-    if dist is not None and only in ("", "fwd_mul"):
+    if gather and dist is not None and only in ("", "fwd_mul"):
         res["gather"] = time_gather(dist, out, n)
     if only in ("", "polymul"):
         res["polymul"] = timed(dist, lambda: ring.multiply(a, b, out=out), steps, warmup)
+        dump_after("polymul")
         if check and mode == "compat":
             checks.append(_check_rows("polymul", a, b, out, n, q))
     if only == "fwd":
         res["fwd"] = timed(dist, lambda: ring.forward_ntt(a, out=out), steps, warmup)
+        dump_after("fwd")
     if only == "inv":
         res["inv"] = timed(dist, lambda: ring.inverse_ntt(a, out=out), steps, warmup)
+        dump_after("inv")
     if not check:
         res["parity_ok"] = "skipped"
     elif mode == "negacyclic":
@@ -773,8 +832,17 @@ def main():
         if rank == 0:
             print(json.dumps({"engine_chain": engine_chain(fhe_gpu)}), flush=True)
         return
-    r = gpu_workload(fhe_gpu, n, args.q, B, K, W, dist, args.only, check=not args.no_check, mode=args.mode)
-    if args.q62 and not args.only:
+    key = args.only or "fwd_mul"
+    dump = (args.dump_outputs, key) if args.dump_outputs and rank == 0 else None
+    # a plain run (neither --full nor --only) times the headline kernel and nothing else
+    full = args.full and not args.only
+    if full or args.only:
+        r = gpu_workload(fhe_gpu, n, args.q, B, K, W, dist, args.only, check=not args.no_check, mode=args.mode,
+                         dump=dump)
+    else:
+        r = gpu_workload(fhe_gpu, n, args.q, B, K, W, dist, "fwd_mul", check=False, mode=args.mode, gather=False,
+                         dump=dump)
+    if args.q62 and full:
         r62 = gpu_workload(fhe_gpu, n, P62, B, max(3, K // 4), 1, dist)
         ach62 = 24 * n * B / (r62["fwd_mul"][1] * 1e-3) / 1e9
         achp62 = 24 * n * B / (r62["polymul"][1] * 1e-3) / 1e9
@@ -789,21 +857,20 @@ def main():
             "polymul_roofline": {"achieved": achp62, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": achp62 / HBM_PEAK_GBS},
         }
-        for key, rl in (("fwd_mul", extra["q62"]["roofline"]), ("polymul", extra["q62"]["polymul_roofline"])):
-            _attach(rl, pmc_traffic(key, n, B, P62), 24 * n * B, r62[key][1])
-    if not args.only:
+        for k62, rl in (("fwd_mul", extra["q62"]["roofline"]), ("polymul", extra["q62"]["polymul_roofline"])):
+            _attach(rl, pmc_traffic(k62, n, B, P62), 24 * n * B, r62[k62][1])
+    if full:
         nk = max(3, K // 4)
         extra["negacyclic"] = negacyclic_workload(fhe_gpu, n, args.q, B, nk, 1, dist)
-    if args.cipher and not args.only:
+    if args.cipher and full:
         extra["cipher"] = cipher_workload(fhe_gpu, max(3, K // 4), 1, dist)
-    if rank == 0 and not args.only and not args.no_host:
+    if rank == 0 and full and not args.no_host:
         extra["host_resident"] = host_resident(fhe_gpu, n, args.q)
         extra["engine_chain"] = engine_chain(fhe_gpu)
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return
-    key = args.only or "fwd_mul"
     wall, kms = r[key]
     units = world * B * K
     value = units / wall
@@ -818,6 +885,7 @@ def main():
         "devices_used": len({(r % max(1, torch.cuda.device_count())) for r in range(world)}),
         "steps": K,
         "warmup": W,
+        "full": full,
         "ms_per_step": wall / K * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -848,7 +916,7 @@ def main():
                                                   "valu_roofline (DESIGN.md section 6)"}
         _attach(line["polymul_roofline"], pmc_traffic("polymul", n, B, args.q), 24 * n * B, pk)
     line.update(extra)
-    if not args.no_cpu and world == 1 and not args.only:
+    if not args.no_cpu and world == 1 and full:
         line["cpu_baseline"] = cpu_baseline(n, args.q, args.cpu_seconds)
         # also one thread (the reference's sequential forward_ntt_batch)
         line["cpu_baseline_1thread"] = cpu_baseline(n, args.q, min(4.0, args.cpu_seconds), threads=1)
