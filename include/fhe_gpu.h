@@ -229,6 +229,34 @@ int fhe_ct_multiply_relin_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level,
                                 const uint64_t *ct2, const uint64_t *rlk_ntt, uint64_t *out, size_t batch,
                                 int where);
 
+/* ---- ciphertext tally (encryption.cpp:1061-1067, 1153-1168, 1327-1460) ---
+ * EncryptionEngine::batch_add / batch_add_tree / tally_votes /
+ * tally_multi_candidate: the sum of `count` ciphertexts of `polys` (1..3)
+ * polynomials each, out[w] = sum_i (ct_i[w] mod q) mod q over the polys * n
+ * words of a ciphertext, canonical.  mod_add is associative and commutative
+ * on residues, so the result equals the reference's sequential and tree
+ * folds bit for bit; input words may be any u64 (mod_add's contract).  One
+ * kernel launch reads every ballot once (two when the ballots are split
+ * across the chip; FHE_TALLY_SPLIT=<S> forces the number of slices, clamped
+ * to count).  count == 0 fails with "Cannot add empty vector of ciphertexts"
+ * (:1329); count == 1 gives that ciphertext reduced mod q (the reference
+ * returns a copy).  accumulate != 0 reads `out` as one more term.  `out` must
+ * not overlap any input (not checked).
+ * fhe_ct_sum_batch  cts [groups][count][polys][n] -> out [groups][polys][n]:
+ *   `groups` independent tallies.  FHE_HOST stages the ballots chunk by
+ *   chunk and folds the chunks with the accumulate flag.  A multi-device
+ *   context splits the groups.
+ * fhe_ct_sum_ptrs   cts is a HOST array of `count` DEVICE pointers, each to
+ *   polys * n words and 16-byte aligned (every ciphertext in its own buffer;
+ *   a pointer may repeat); out is a device buffer.  The table is copied
+ *   before the call returns: the caller may free it at once.  On a
+ *   multi-device context the call runs on the device that holds cts[0], and
+ *   every pointer must be memory of that device. */
+int fhe_ct_sum_batch(fhe_ctx *ctx, const uint64_t *cts, uint32_t polys, size_t count, size_t groups, int accumulate,
+                     uint64_t *out, int where);
+int fhe_ct_sum_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, uint32_t polys, size_t count, int accumulate,
+                    uint64_t *out);
+
 /* ---- TFHE bootstrapping pieces (bootstrap_engine.cpp) --------------------
  * GLWE [batch][k+1][n] as above; LWE masks [batch][dim], bodies [batch].
  * fhe_glwe_rotate_batch    multiply_glwe_by_monomial (:249-261) by X^rot[c].

@@ -177,6 +177,14 @@ hipError_t launch_mul_scalar(const ModConsts &m, const uint64_t *a, uint64_t sc,
                              size_t n, hipStream_t s);
 hipError_t launch_ml_montmul(const uint64_t consts[7], const uint64_t *a, const uint64_t *b, uint64_t *c, size_t n,
                              hipStream_t s);
+// Segmented ciphertext sum (tally.hip): one pass of k_ct_sum.  src is
+// [groups][count][words] u64, or with ptr_table a device array of `count`
+// pointers to `words` u64 each (16-byte aligned, groups == 1).  Slice y of
+// `slices` sums ballots [y per, min(count, (y+1) per)) into row y of
+// out [groups][slices][words]; accumulate (slices == 1 only) reads out as one
+// more term.  words even, q odd.
+hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
+                         size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s);
 // Tensor product of NTT-form ciphertexts: x, y [batch][2][n] -> [batch][3][n]
 hipError_t launch_tensor_ntt(const ModConsts &m, const uint64_t *x, const uint64_t *y, uint64_t *out, uint32_t n,
                              size_t batch, hipStream_t s);

@@ -1,0 +1,109 @@
+// tally.hip -- segmented sum of ciphertexts in one HBM pass.
+//
+//   k_ct_sum : out[g][w] = sum_{i<count} (in[g][i][w] mod q) mod q, canonical,
+//              w < words = polys N.  EncryptionEngine::batch_add /
+//              batch_add_tree (encryption.cpp:1327-1460), tally_votes
+//              (:1061-1067) and tally_multi_candidate (:1153-1168): a fold of
+//              add() (:700-730), whose coefficients are mod_add
+//              (modular_arithmetic.cpp:122-135).  mod_add of canonical residues
+//              is associative and commutative, so any order of summation gives
+//              the reference's words bit for bit.
+//
+// Layout: a lane owns one 16-byte column (two u64) of one group's output and
+// walks the ballots of its slice, kUnroll non-temporal 16-byte loads in
+// flight.  grid = (column blocks, slices, groups): slice blockIdx.y sums
+// ballots [y per, (y+1) per) and writes row y of the group's [slices][words]
+// partials; a second launch of the same kernel over those rows (contiguous
+// form, count = slices) folds them.  Two addressing forms: contiguous
+// [groups][count][words], or a device table of `count` pointers (one group),
+// read as wave-uniform scalar loads.
+//
+// Accumulation: the raw words are summed into a 128-bit (hi:lo) integer and
+// reduced once per column.  Statically that is 4 VALU per word in the loop as
+// compiled for gfx950 (v_lshl_add_u64, v_cmp_lt_u64, v_cndmask, v_lshl_add_u64
+// into hi) against about 10 for the reduce-then-mod_add form (compare with q,
+// 64-bit add, carry compare, compare with q, 64-bit subtract, two selects, on
+// 32-bit halves) plus its divergent slow path for words >= q; either is far
+// below what the 16 bytes per lane and ballot cost in HBM time.  The single
+// reduction at the end,
+// hi 2^64 + lo = wmont(hi, 2^128 mod q) + lo (mod q), is exact for any odd
+// q < 2^64 and any count < 2^64 (as lwe.hip's split key-switch sum).
+#include "fhe_internal.hpp"
+
+namespace FHE_NS {
+
+static constexpr int kBlock = 256;
+static constexpr int kUnroll = 8;
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+struct TallyAcc {
+    uint64_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+    __device__ __forceinline__ void add(u64x2 v) {
+        lo0 += v.x;
+        hi0 += lo0 < v.x;
+        lo1 += v.y;
+        hi1 += lo1 < v.y;
+    }
+};
+
+__device__ __forceinline__ uint64_t fold128(uint64_t hi, uint64_t lo, const ModConsts &m) {
+    const uint64_t l = mod64_slow(lo, m.q, m.mu);
+    if (hi == 0) return l;
+    const uint64_t h = wmont(mod64_slow(hi, m.q, m.mu), m.r2, m.q, m.qinv);  // hi 2^64 mod q
+    return wadd(h, l, m.q);
+}
+
+// PTR = false: src is [groups][count][words] u64.  PTR = true: src is a table
+// of `count` pointers to `words` u64 each (gridDim.z == 1).
+template <bool PTR>
+__global__ void __launch_bounds__(kBlock)
+k_ct_sum(const void *__restrict__ src, uint64_t *__restrict__ out, size_t cols, size_t count, size_t per,
+         size_t groups, int accumulate, ModConsts m) {
+    const size_t i0 = (size_t)blockIdx.y * per;
+    const size_t i1 = i0 + per < count ? i0 + per : count;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t g = blockIdx.z; g < groups; g += gridDim.z) {
+        u64x2 *const dst = reinterpret_cast<u64x2 *>(out) + (g * gridDim.y + blockIdx.y) * cols;
+        for (size_t col = (size_t)blockIdx.x * kBlock + threadIdx.x; col < cols; col += stride) {
+            auto row = [&](size_t i) -> const u64x2 * {
+                if (PTR) return reinterpret_cast<const u64x2 *const *>(src)[i] + col;
+                return reinterpret_cast<const u64x2 *>(src) + (g * count + i) * cols + col;
+            };
+            TallyAcc a;
+            if (accumulate) a.add(dst[col]);
+            size_t i = i0;
+            for (; i + kUnroll <= i1; i += kUnroll) {
+                u64x2 v[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) v[u] = __builtin_nontemporal_load(row(i + u));
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) a.add(v[u]);
+            }
+            for (; i < i1; ++i) a.add(__builtin_nontemporal_load(row(i)));
+            u64x2 r;
+            r.x = fold128(a.hi0, a.lo0, m);
+            r.y = fold128(a.hi1, a.lo1, m);
+            dst[col] = r;
+        }
+    }
+}
+
+// One pass: `slices` rows per group into out ([groups][slices][cols 2] u64).
+hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
+                         size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s) {
+    if (words == 0 || count == 0 || groups == 0) return hipSuccess;
+    if ((words & 1) || !(m.q & 1) || per == 0 || slices == 0 || slices > 65535 || (slices - 1) * per >= count ||
+        slices * per < count || (ptr_table && groups != 1) || (accumulate && slices != 1))
+        return hipErrorInvalidValue;
+    const size_t cols = words / 2;
+    size_t gx = (cols + kBlock - 1) / kBlock;
+    if (gx > 65535) gx = 65535;  // grid-stride beyond
+    const dim3 grid((unsigned)gx, (unsigned)slices, (unsigned)(groups < 65535 ? groups : 65535));
+    if (ptr_table)
+        hipLaunchKernelGGL(k_ct_sum<true>, grid, dim3(kBlock), 0, s, src, out, cols, count, per, groups, accumulate, m);
+    else
+        hipLaunchKernelGGL(k_ct_sum<false>, grid, dim3(kBlock), 0, s, src, out, cols, count, per, groups, accumulate, m);
+    return hipGetLastError();
+}
+
+}  // namespace FHE_NS

@@ -113,6 +113,8 @@ SIGNATURES = [
     ("fhe_poly_sub_batch", C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_poly_neg_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_poly_mul_scalar_batch", C.c_int, [vp, vp, C.c_uint64, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_sum_batch", C.c_int, [vp, vp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_int]),
+    ("fhe_ct_sum_ptrs", C.c_int, [vp, vp, C.c_uint32, C.c_size_t, C.c_int, vp]),
     ("fhe_ggsw_prepare", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int]),
     ("fhe_external_product_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
@@ -508,6 +510,61 @@ class PolynomialRing(NTTProcessor):
         w = _where(ba, bo)
         self._bind_stream(w)
         _check(lib().fhe_poly_mul_scalar_batch(self._h, ba.ptr, scalar, bo.ptr, nb, w))
+        return out
+
+    def sum_batch(self, a, out=None, accumulate: bool = False, grouped=None):
+        """Sum over the ballot axis in one launch (batch_add / batch_add_tree,
+        encryption.cpp:1327-1460): a [count, ..., n] -> [..., n], or
+        a [groups, count, ..., n] -> [groups, ..., n]; `...` is empty or the
+        1..3 polynomials of a ciphertext.  grouped=None reads a 4-d input as
+        grouped.  accumulate: `out` is one more term of each sum."""
+        a = _as_u64(a)
+        shape = tuple(a.shape)
+        grouped = len(shape) == 4 if grouped is None else bool(grouped)
+        lead = 2 if grouped else 1
+        if len(shape) < lead + 1 or shape[-1] != self.degree:
+            raise FHEError(-5, "Coefficient count must equal polynomial degree")
+        groups, count = (shape[0], shape[1]) if grouped else (1, shape[0])
+        polys = 1
+        for d in shape[lead:-1]:
+            polys *= d
+        oshape = ((groups,) if grouped else ()) + shape[lead:]
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = _empty(a, oshape)
+        elif tuple(out.shape) != oshape:
+            raise FHEError(-9, f"out must have shape {list(oshape)}")
+        ba, bo = _Buf(a), _Buf(out, True)
+        w = _where(ba, bo)
+        self._bind_stream(w)
+        _check(lib().fhe_ct_sum_batch(self._h, ba.ptr, polys, count, groups, int(bool(accumulate)), bo.ptr, w))
+        return out
+
+    def sum_buffers(self, bufs, out=None, accumulate: bool = False):
+        """sum_batch over separately allocated device tensors [..., n] of one
+        shape (1..3 polynomials each); a tensor may be listed twice."""
+        bufs = list(bufs)
+        if not bufs:
+            raise FHEError(-9, "Cannot add empty vector of ciphertexts")
+        shape = tuple(bufs[0].shape)
+        if not shape or shape[-1] != self.degree:
+            raise FHEError(-5, "Coefficient count must equal polynomial degree")
+        if any(tuple(b.shape) != shape for b in bufs):
+            raise FHEError(-9, "operand shapes differ")
+        polys = 1
+        for d in shape[:-1]:
+            polys *= d
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = torch.empty_like(bufs[0])
+        bs, bo = [_Buf(b) for b in bufs], _Buf(out, True)
+        if _where(bo, *bs) != FHE_DEVICE:
+            raise FHEError(-9, "sum_buffers takes device tensors (stack host arrays for sum_batch)")
+        self._bind_stream(FHE_DEVICE)
+        table = (C.c_void_p * len(bs))(*[b.ptr for b in bs])
+        _check(lib().fhe_ct_sum_ptrs(self._h, table, polys, len(bs), int(bool(accumulate)), bo.ptr))
         return out
 
     def to_ntt(self, p, out=None):
@@ -968,6 +1025,34 @@ class EncryptionEngine:
         """add (:594-617): componentwise mod_add of (c0, c1)."""
         ct1, ct2 = self._pair(ct1, ct2)
         return self.ring.add(ct1, ct2, out)
+
+    def batch_add(self, cts, out=None):
+        """batch_add / batch_add_tree (:1327-1460): the sum of the ciphertexts
+        cts [count, 2 | 3, n] (or a list of them; a list of device tensors is
+        summed in place, no copy) -> [2 | 3, n], in one launch."""
+        r = self.ring
+        if isinstance(cts, (list, tuple)):
+            if len(cts) == 0:
+                raise FHEError(-9, "Cannot add empty vector of ciphertexts")
+            if all(_is_tensor(c) for c in cts):
+                for c in cts:
+                    if len(c.shape) != 2 or c.shape[0] not in (2, 3):
+                        raise FHEError(-9, "ciphertexts must be [2, n] or [3, n]")
+                return r.sum_buffers(cts, out)
+            cts = np.stack([np.asarray(c, dtype=np.uint64) for c in cts])
+        cts = _as_u64(cts)
+        if len(cts.shape) != 3 or cts.shape[1] not in (2, 3):
+            raise FHEError(-9, "ciphertexts must be [count, 2, n] or [count, 3, n]")
+        return r.sum_batch(cts, out, grouped=False)
+
+    tally_votes = batch_add  # tally_votes (:1061-1067) is batch_add_tree
+
+    def tally_multi_candidate(self, cts, num_candidates: int, out=None):
+        """tally_multi_candidate (:1153-1168): packed ballots, one slot per
+        candidate; the sum keeps the slots."""
+        if num_candidates > self.ring.degree:
+            raise FHEError(-9, "Number of candidates exceeds polynomial degree")
+        return self.batch_add(cts, out)
 
     def subtract(self, ct1, ct2, out=None):
         """subtract (:692-714)."""

@@ -225,6 +225,17 @@ export interface FHEEngine {
   dispose(): void;
 }
 
+/** Ballot aggregation (EncryptionEngine::tally_votes, tally_multi_candidate,
+ * update_tally, tally_weighted_votes; encryption.cpp:1061-1168): every sum is
+ * one device launch over all ballots. */
+export interface FHETallyEngine extends FHEEngine {
+  tallyVotes(ballots: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  tallyMultiCandidate(ballots: Ciphertext[], numCandidates: number, progress?: ProgressCallback): Promise<Ciphertext>;
+  updateTally(tally: Ciphertext, ballot: Ciphertext): Promise<Ciphertext>;
+  tallyWeightedVotes(ballots: Ciphertext[], weights: Ciphertext[], ek: EvaluationKey,
+    progress?: ProgressCallback): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -232,7 +243,7 @@ export interface EngineOptions {
   devices?: number[];
 }
 
-export declare class FHEEngineImpl implements FHEEngine {
+export declare class FHEEngineImpl implements FHETallyEngine {
   constructor(params: ParameterSet, options?: EngineOptions);
   generateSecretKey(options?: KeyGenerationOptions): Promise<SecretKey>;
   generatePublicKey(sk: SecretKey): Promise<PublicKey>;
@@ -278,6 +289,11 @@ export declare class FHEEngineImpl implements FHEEngine {
   getHardwareCapabilities(): HardwareCapabilities;
   getSlotCount(): number;
   dispose(): void;
+  tallyVotes(ballots: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  tallyMultiCandidate(ballots: Ciphertext[], numCandidates: number, progress?: ProgressCallback): Promise<Ciphertext>;
+  updateTally(tally: Ciphertext, ballot: Ciphertext): Promise<Ciphertext>;
+  tallyWeightedVotes(ballots: Ciphertext[], weights: Ciphertext[], ek: EvaluationKey,
+    progress?: ProgressCallback): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension). */
   deviceBuffer(handle: unknown): DeviceBuffer | undefined;
 }
@@ -336,6 +352,10 @@ export declare class NttContext {
   sub(a: Words, b: Words, out: Words): Words;
   negate(a: Words, out: Words): Words;
   mulScalar(a: Words, s: bigint, out: Words): Words;
+  /** out = the sum of the ciphertexts in `buffers` (1..3 polynomials each, out.words
+   * words; an entry may repeat; out is none of them): one launch (fhe_ct_sum_ptrs). */
+  sum(buffers: DeviceBuffer[], out: DeviceBuffer): DeviceBuffer;
+  sumAsync(buffers: DeviceBuffer[], out: DeviceBuffer): Promise<DeviceBuffer>;
   ctMultiply(ct1: Words, ct2: Words, out: Words, isNtt?: number): Words;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;

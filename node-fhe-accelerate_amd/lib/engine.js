@@ -592,19 +592,101 @@ function makeEngineClass(native) {
     }
     /** add_scalar (:685-688) */
     async addScalar(ct, value) { return this.addPlain(ct, this.createPlaintext(value)); }
+    /** The checks a chain of add() makes over a whole list, in its order: the
+     *  running sum keeps the first key and degree and is in coefficient
+     *  form from the first addition on. */
+    _sumInputs(cts) {
+      const first = this._rlwe(cts[0]);
+      const run = { keyId: cts[0].keyId, isNtt: cts[0].isNtt, comps: first.comps };
+      const bufs = [first.buf];
+      let packed = first.packed;
+      for (let i = 1; i < cts.length; i++) {
+        const b = this._rlwe(cts[i]);
+        this._sameKey(run, cts[i], 'add');
+        if (run.isNtt !== cts[i].isNtt) throw new FHEError('Cannot combine ciphertexts in different representations (NTT vs coefficient)', FHEErrorCode.INVALID_PARAMETERS);
+        if (run.comps !== b.comps) throw new FHEError('ciphertext degrees differ', FHEErrorCode.INVALID_PARAMETERS);
+        run.isNtt = false;
+        run.comps = cts[0].degree + 1;
+        bufs.push(b.buf);
+        packed = packed || b.packed;
+      }
+      return { bufs, packed, comps: run.comps };
+    }
+    /** One launch over every input (fhe_ct_sum_ptrs); the words equal the chain's and the tree's */
+    async _sum(cts, noiseBudget) {
+      const f = this._sumInputs(cts);
+      const out = this._buf(f.comps * this._n);
+      await this._ctx.sumAsync(f.bufs, out);
+      return this._ct(out, cts[0].keyId, noiseBudget, cts[0].degree, { packed: f.packed });
+    }
+    /** batch_add (:1327-1364) as a chain of add(): budget min - 1 per input */
     async batchAdd(cts, progress) {
       this._check();
       if (!Array.isArray(cts) || cts.length === 0) throw new FHEError('Empty array', FHEErrorCode.INVALID_PARAMETERS);
+      if (cts.length === 1) return cts[0];
       const start = Date.now();
-      let r = cts[0];
-      for (let i = 1; i < cts.length; i++) {
-        r = await this.add(r, cts[i]);
-        if (progress) {
-          progress({ stage: 'batch_add', current: i + 1, total: cts.length, elapsedMs: Date.now() - start,
-            progressPercent: ((i + 1) / cts.length) * 100 });
-        }
+      let budget = cts[0].noiseBudget;
+      for (let i = 1; i < cts.length; i++) budget = Math.min(budget, cts[i].noiseBudget) - 1;
+      const r = await guard(async () => this._sum(cts, budget));
+      for (let i = 1; progress && i < cts.length; i++) {
+        progress({ stage: 'batch_add', current: i + 1, total: cts.length, elapsedMs: Date.now() - start,
+          progressPercent: ((i + 1) / cts.length) * 100 });
       }
       return r;
+    }
+
+    // ---- ballot aggregation (encryption.cpp:1061-1168)
+    /** tally_votes (:1061-1067) = batch_add_tree (:1366-1458): budget min - 1
+     *  per tree level, an odd element carried up unchanged; progress counts
+     *  the count - 1 additions */
+    async tallyVotes(ballots, progress) {
+      this._check();
+      if (!Array.isArray(ballots) || ballots.length === 0) {
+        throw new FHEError('Cannot add empty vector of ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      const start = Date.now();
+      let level = ballots.map((b) => b.noiseBudget);
+      while (level.length > 1) {
+        const next = [];
+        for (let i = 0; i + 1 < level.length; i += 2) next.push(Math.min(level[i], level[i + 1]) - 1);
+        if (level.length % 2 === 1) next.push(level[level.length - 1]);
+        level = next;
+      }
+      const r = await guard(async () => this._sum(ballots, level[0]));
+      const total = ballots.length - 1;
+      for (let i = 1; progress && i <= total; i++) {
+        progress({ stage: 'tally_votes', current: i, total, elapsedMs: Date.now() - start, progressPercent: (i / total) * 100 });
+      }
+      return r;
+    }
+    /** tally_multi_candidate (:1153-1168): packed ballots, one slot per candidate */
+    async tallyMultiCandidate(ballots, numCandidates, progress) {
+      this._check();
+      if (numCandidates > this._n) {
+        throw new FHEError('Number of candidates exceeds polynomial degree', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      return this.tallyVotes(ballots, progress);
+    }
+    /** update_tally (:1145-1151) */
+    async updateTally(tally, ballot) { return this.add(tally, ballot); }
+    /** tally_weighted_votes (:1069-1110): multiply + relinearize per ballot
+     *  (progress every 100, of 2 * count), then one tally (progress count +
+     *  completed of count + (count - 1)) */
+    async tallyWeightedVotes(ballots, weights, ek, progress) {
+      this._check();
+      if (!Array.isArray(ballots) || !Array.isArray(weights) || ballots.length !== weights.length) {
+        throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (ballots.length === 0) throw new FHEError('Cannot tally empty ballot list', FHEErrorCode.INVALID_PARAMETERS);
+      const start = Date.now(), total = ballots.length;
+      const report = (current, of) => progress({ stage: 'tally_weighted_votes', current, total: of,
+        elapsedMs: Date.now() - start, progressPercent: (current / of) * 100 });
+      const weighted = [];
+      for (let i = 0; i < total; i++) {
+        weighted.push(await this.multiplyRelin(ballots[i], weights[i], ek));
+        if (progress && (i + 1) % 100 === 0) report(i + 1, total * 2);
+      }
+      return this.tallyVotes(weighted, progress ? (p) => report(total + p.current, total + p.total) : undefined);
     }
 
     // ---- multiplicative operations (encryption.cpp:737-980)

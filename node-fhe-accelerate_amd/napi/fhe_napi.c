@@ -623,6 +623,8 @@ struct job {
     int nref;
     dblock *blks[MAXP]; /* async path: device blocks pinned until completion */
     int nblk;
+    dblock **xblks;     /* async path: the pinned blocks of a buffer list (sum) */
+    size_t nxblk;
     napi_ref ret;       /* async path */
     napi_deferred def;
     napi_async_work work;
@@ -677,6 +679,8 @@ static void job_free(napi_env env, job *j) {
     /* after the job's final stream synchronisation: a buffer freed by the
      * caller meanwhile is returned to the pool only now */
     for (int i = 0; i < j->nblk; ++i) dblock_release(j->blks[i]);
+    for (size_t i = 0; i < j->nxblk; ++i) dblock_release(j->xblks[i]);
+    free(j->xblks);
     if (j->ret) napi_delete_reference(env, j->ret);
     free(j->owned);
     free(j);
@@ -874,6 +878,56 @@ static napi_value ctx_mul_scalar(napi_env env, napi_callback_info info) {
     job *j = job_new(&k, run_mul_scalar, NULL);
     j->p[0] = a; j->p[1] = o; j->v[0] = s; j->batch = na / k.n;
     return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+
+/* sum(buffers[], out): out = the sum of the ciphertexts in `buffers`
+ * (fhe_ct_sum_ptrs: batch_add / batch_add_tree, encryption.cpp:1327-1460), one
+ * launch.  Every entry is a DeviceBuffer of this context with out.words =
+ * polys * n words (polys 1..3); an entry may repeat; out is none of them. */
+static int run_sum(job *j) {
+    return fhe_ct_sum_ptrs(j->c, (const uint64_t *const *)j->owned, (uint32_t)j->v[0], j->batch, 0, j->p[0]);
+}
+static napi_value ctx_sum(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 2, &k)) return NULL;
+    bool is_arr = false;
+    uint32_t cnt = 0;
+    uint64_t *o;
+    size_t no;
+    if (k.argc < 2 || napi_is_array(env, k.argv[0], &is_arr) != napi_ok || !is_arr ||
+        napi_get_array_length(env, k.argv[0], &cnt) != napi_ok || arr_arg(env, &k, 1, &o, &no) ||
+        k.where != FHE_DEVICE)
+        return bad_args(env, "sum(buffers[], out): DeviceBuffers of this context"), NULL;
+    if (cnt == 0) return range_err(env, "Cannot add empty vector of ciphertexts");
+    if (no % k.n || no / k.n < 1 || no / k.n > 3) return range_err(env, "a ciphertext has 1 to 3 polynomials");
+    uint64_t **tab = (uint64_t **)malloc(cnt * sizeof *tab);
+    dblock **blks = k.async ? (dblock **)malloc(cnt * sizeof *blks) : NULL;
+    if (!tab || (k.async && !blks)) {
+        free(tab);
+        free(blks);
+        napi_throw_error(env, "NATIVE_ERROR", "out of memory");
+        return NULL;
+    }
+    for (uint32_t i = 0; i < cnt; ++i) {
+        napi_value e;
+        dbuf *d = napi_get_element(env, k.argv[0], i, &e) == napi_ok ? unwrap_buf(env, e) : NULL;
+        if (!d || !d->blk || d->blk->owner != k.k || d->words != no || dbuf_ptr(d) == o) {
+            free(tab);
+            free(blks);
+            return bad_args(env, "sum(buffers[], out): every entry a DeviceBuffer of out's size, none of them out"), NULL;
+        }
+        tab[i] = dbuf_ptr(d);
+        if (blks) blks[i] = d->blk;
+    }
+    job *j = job_new(&k, run_sum, NULL);
+    j->owned = (uint64_t *)tab;
+    j->p[0] = o; j->v[0] = no / k.n; j->batch = cnt;
+    if (blks) {  /* pinned like the blocks of arr_arg (job_go) */
+        for (uint32_t i = 0; i < cnt; ++i) blks[i]->refs++;
+        j->xblks = blks;
+        j->nxblk = cnt;
+    }
+    return job_go(env, &k, j, k.argv[1], k.argv, 2);
 }
 
 /* externalProduct(glwe, ggswCoeff, baseLog, level, out): k = 1, the key
@@ -1473,6 +1527,7 @@ static napi_value init(napi_env env, napi_value exports) {
         M("sub", ctx_sub),
         M("negate", ctx_negate),
         M("mulScalar", ctx_mul_scalar),
+        M("sum", ctx_sum),
         M("forwardMul", ctx_fwd_mul),
         M("externalProduct", ctx_ext_product),
         M("prepareGgsw", ctx_prep_ggsw),
