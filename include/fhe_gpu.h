@@ -257,6 +257,53 @@ int fhe_ct_sum_batch(fhe_ctx *ctx, const uint64_t *cts, uint32_t polys, size_t c
 int fhe_ct_sum_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, uint32_t polys, size_t count, int accumulate,
                     uint64_t *out);
 
+/* ---- ciphertext inner product (encryption.cpp:1069-1110, :737-798) -------
+ * out[g] = sum_i multiply(a[g][i], b[g][i]), the degree-2 sum folded by
+ * add(): the weighted tally of EncryptionEngine::tally_weighted_votes before
+ * its relinearisation, an encrypted dot product, a sum of squares.  The
+ * inverse transform is a Z_q-linear map, so on canonical residues
+ *   sum_i multiply(a_i, b_i) = ( inv(sum X0_i Y0_i),
+ *                                inv(sum (X0_i Y1_i + X1_i Y0_i)),
+ *                                inv(sum X1_i Y1_i) )
+ * holds bit for bit: the call runs four forward transforms per pair and three
+ * inverse transforms per slice of pairs, writes no intermediate ciphertext,
+ * and its words equal fhe_ct_multiply_batch followed by fhe_ct_sum_batch
+ * (polys = 3).  Inputs may be any u64 (read as x mod q); outputs are
+ * canonical.  The pairs are split into slices across the chip and the partial
+ * rows folded by the tally kernel; FHE_DOT_SPLIT=<S> forces the number of
+ * slices (read per call, clamped to count).  While three times the slices
+ * still fit on the chip (few pairs), each of the three sums of a slice runs on
+ * a workgroup of its own; FHE_DOT_COMPONENTS=0|1 forces that off or on.
+ * Between the two (one pair per slice, too many slices for that) contiguous
+ * operands take the multiply kernel into the partial rows: there the fused
+ * kernel would be a multiply that also parks its spectra.
+ * is_ntt != 0: the inputs are
+ * NTT-domain and so is the result (no transform runs).  count == 0 fails with
+ * "Cannot tally empty ballot list" (:1080).  accumulate != 0 reads `out` as
+ * one more degree-2 term (any u64 words).  `out` must not overlap an input.
+ * Shapes outside the fused family (n > 16384, or q >= 2^62) run composed:
+ * chunks of the unfused multiply into a bounded temporary, each folded into
+ * `out` by the tally kernel -- bit-exact, not expected to be fast.
+ *
+ * Relinearising the sum once (lazy relinearisation) is NOT word-identical to
+ * the reference's relinearise-per-ballot fold: the digit decomposition of c2
+ * is not linear.  It decrypts to the same plaintext, with less noise (one
+ * key-switch error instead of `count`).
+ * fhe_ct_dot_batch  a, b [groups][count][2][n] -> out [groups][3][n]:
+ *   `groups` independent inner products.  FHE_HOST stages chunks of pairs and
+ *   folds them with the accumulate flag.  A multi-device context splits the
+ *   groups.  Device buffers must be 16-byte aligned.
+ * fhe_ct_dot_ptrs   a, b are HOST arrays of `count` DEVICE pointers, each to
+ *   one ciphertext (2 n words, 16-byte aligned); pointers may repeat and
+ *   a[i] == b[i] gives a square; out is a device buffer.  The tables are
+ *   copied before the call returns.  On a multi-device context the call runs
+ *   on the device that holds a[0], and every pointer must be memory of that
+ *   device. */
+int fhe_ct_dot_batch(fhe_ctx *ctx, const uint64_t *a, const uint64_t *b, size_t count, size_t groups, int is_ntt,
+                     int accumulate, uint64_t *out, int where);
+int fhe_ct_dot_ptrs(fhe_ctx *ctx, const uint64_t *const *a, const uint64_t *const *b, size_t count, int is_ntt,
+                    int accumulate, uint64_t *out);
+
 /* ---- TFHE bootstrapping pieces (bootstrap_engine.cpp) --------------------
  * GLWE [batch][k+1][n] as above; LWE masks [batch][dim], bodies [batch].
  * fhe_glwe_rotate_batch    multiply_glwe_by_monomial (:249-261) by X^rot[c].

@@ -185,6 +185,21 @@ hipError_t launch_ml_montmul(const uint64_t consts[7], const uint64_t *a, const 
 // more term.  words even, q odd.
 hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
                          size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s);
+// Ciphertext inner product (dot.hip).  a, b are [groups][count][2][n] u64, or
+// with ptr_table device arrays of `count` pointers to 2 n u64 each (groups ==
+// 1).  Slice y of `slices` covers pairs [y per, min(count, (y+1) per)) and
+// writes row y of dst [groups][slices][3][n], canonical; launch_ct_sum folds
+// the rows.  launch_ct_dot: coefficient form, the fused family only (n <=
+// 16384, q < 2^62), with a workspace of ct_dot_ws_bytes; ct_dot_resident is
+// the number of slices one launch keeps resident; by_component runs three
+// workgroups per slice, one per component of the sum.  launch_ct_dot_ntt:
+// NTT-domain inputs, any n and odd q, 16-byte aligned buffers.
+size_t ct_dot_resident(const Plan &p);
+size_t ct_dot_ws_bytes(const Plan &p, size_t slices, size_t groups);
+hipError_t launch_ct_dot(const Plan &p, const void *a, const void *b, bool ptr_table, void *ws, uint64_t *dst,
+                         size_t count, size_t per, size_t slices, size_t groups, bool by_component);
+hipError_t launch_ct_dot_ntt(const ModConsts &m, const void *a, const void *b, bool ptr_table, uint64_t *dst, uint32_t n,
+                             size_t count, size_t per, size_t slices, size_t groups, hipStream_t s);
 // Tensor product of NTT-form ciphertexts: x, y [batch][2][n] -> [batch][3][n]
 hipError_t launch_tensor_ntt(const ModConsts &m, const uint64_t *x, const uint64_t *y, uint64_t *out, uint32_t n,
                              size_t batch, hipStream_t s);

@@ -115,6 +115,8 @@ SIGNATURES = [
     ("fhe_poly_mul_scalar_batch", C.c_int, [vp, vp, C.c_uint64, vp, C.c_size_t, C.c_int]),
     ("fhe_ct_sum_batch", C.c_int, [vp, vp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_int]),
     ("fhe_ct_sum_ptrs", C.c_int, [vp, vp, C.c_uint32, C.c_size_t, C.c_int, vp]),
+    ("fhe_ct_dot_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_int]),
+    ("fhe_ct_dot_ptrs", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
     ("fhe_ggsw_prepare", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int]),
     ("fhe_external_product_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
@@ -1053,6 +1055,91 @@ class EncryptionEngine:
         if num_candidates > self.ring.degree:
             raise FHEError(-9, "Number of candidates exceeds polynomial degree")
         return self.batch_add(cts, out)
+
+    def dot(self, cts1, cts2, is_ntt: bool = False, out=None, accumulate: bool = False, grouped=None):
+        """Ciphertext inner product in one fused launch: the degree-2 sum
+        sum_i multiply(cts1[i], cts2[i]) folded by add(), with no intermediate
+        ciphertexts.  cts [count, 2, n] -> [3, n], or [groups, count, 2, n] ->
+        [groups, 3, n]; grouped=None reads a 4-d input as grouped.  Words equal
+        multiply() followed by batch_add().  accumulate: `out` is one more
+        degree-2 term of each sum."""
+        r = self.ring
+        cts1, cts2 = _as_u64(cts1), _as_u64(cts2)
+        shape = tuple(cts1.shape)
+        grouped = len(shape) == 4 if grouped is None else bool(grouped)
+        lead = 2 if grouped else 1
+        if len(shape) != lead + 2 or shape[lead:] != (2, r.degree):
+            raise FHEError(-9, "ciphertexts must be [count, 2, n] or [groups, count, 2, n]")
+        if tuple(cts2.shape) != shape:
+            raise FHEError(-9, "ciphertext shapes differ")
+        groups, count = (shape[0], shape[1]) if grouped else (1, shape[0])
+        if count == 0:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        oshape = ((groups,) if grouped else ()) + (3, r.degree)
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = _empty(cts1, oshape)
+        elif tuple(out.shape) != oshape:
+            raise FHEError(-9, f"out must have shape {list(oshape)}")
+        b1, b2, bo = _Buf(cts1), _Buf(cts2), _Buf(out, True)
+        w = _where(b1, b2, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_dot_batch(r._h, b1.ptr, b2.ptr, count, groups, int(bool(is_ntt)), int(bool(accumulate)),
+                                      bo.ptr, w))
+        return out
+
+    def dot_buffers(self, bufs1, bufs2, is_ntt: bool = False, out=None, accumulate: bool = False):
+        """dot over separately allocated device ciphertexts [2, n]; a tensor
+        may be listed twice, and bufs1[i] is bufs2[i] gives a square."""
+        r = self.ring
+        bufs1, bufs2 = list(bufs1), list(bufs2)
+        if len(bufs1) != len(bufs2):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if not bufs1:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        if any(tuple(b.shape) != (2, r.degree) for b in bufs1 + bufs2):
+            raise FHEError(-9, "ciphertexts must be [2, n]")
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = torch.empty((3, r.degree), dtype=bufs1[0].dtype, device=bufs1[0].device)
+        elif tuple(out.shape) != (3, r.degree):
+            raise FHEError(-9, f"out must have shape {[3, r.degree]}")
+        b1, b2, bo = [_Buf(b) for b in bufs1], [_Buf(b) for b in bufs2], _Buf(out, True)
+        if _where(bo, *b1, *b2) != FHE_DEVICE:
+            raise FHEError(-9, "dot_buffers takes device tensors (stack host arrays for dot)")
+        r._bind_stream(FHE_DEVICE)
+        t1 = (C.c_void_p * len(b1))(*[b.ptr for b in b1])
+        t2 = (C.c_void_p * len(b2))(*[b.ptr for b in b2])
+        _check(lib().fhe_ct_dot_ptrs(r._h, t1, t2, len(b1), int(bool(is_ntt)), int(bool(accumulate)), bo.ptr))
+        return out
+
+    def tally_weighted_votes(self, ballots, weights, ek: EvaluationKey, relinearize: str = "each", out=None):
+        """tally_weighted_votes (:1069-1110): sum_i ballots[i] * weights[i] as
+        a degree-1 ciphertext [2, n].  relinearize="each" is the reference's
+        multiply_relin per ballot followed by batch_add (its words);
+        relinearize="once" is dot() followed by one relinearisation: the same
+        plaintext with less noise, not the same words (the digit decomposition
+        is not linear)."""
+        if relinearize not in ("each", "once"):
+            raise FHEError(-9, "relinearize must be 'each' or 'once'")
+        if len(ballots) != len(weights):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if len(ballots) == 0:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        lists = isinstance(ballots, (list, tuple)) and isinstance(weights, (list, tuple))
+        if lists and all(_is_tensor(c) for c in list(ballots) + list(weights)):
+            if relinearize == "once":
+                return self.relinearize(self.dot_buffers(ballots, weights), ek, out)
+            ballots, weights = torch.stack(list(ballots)), torch.stack(list(weights))
+        if isinstance(ballots, (list, tuple)):
+            ballots = np.stack([np.asarray(c, dtype=np.uint64) for c in ballots])
+        if isinstance(weights, (list, tuple)):
+            weights = np.stack([np.asarray(c, dtype=np.uint64) for c in weights])
+        if relinearize == "once":
+            return self.relinearize(self.dot(ballots, weights, grouped=False), ek, out)
+        return self.batch_add(self.multiply_relin(ballots, weights, ek), out)
 
     def subtract(self, ct1, ct2, out=None):
         """subtract (:692-714)."""

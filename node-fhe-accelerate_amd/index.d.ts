@@ -236,6 +236,21 @@ export interface FHETallyEngine extends FHEEngine {
     progress?: ProgressCallback): Promise<Ciphertext>;
 }
 
+/** tallyWeightedVotes' fifth argument.  'each' (default): multiply and
+ * relinearise per ballot, the reference's words.  'once': the fused degree-2
+ * sum (dotProduct) and one relinearisation: the same plaintext with less
+ * noise, not the same words (the digit decomposition is not linear). */
+export interface TallyWeightedOptions {
+  relinearize?: 'each' | 'once';
+}
+
+/** Ciphertext inner product: sum_i multiply(cts1[i], cts2[i]) as one degree-2
+ * ciphertext in one fused launch (fhe_ct_dot_ptrs), word-identical to the
+ * chain of multiply() and add(). */
+export interface FHEDotEngine extends FHETallyEngine {
+  dotProduct(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -293,7 +308,8 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   tallyMultiCandidate(ballots: Ciphertext[], numCandidates: number, progress?: ProgressCallback): Promise<Ciphertext>;
   updateTally(tally: Ciphertext, ballot: Ciphertext): Promise<Ciphertext>;
   tallyWeightedVotes(ballots: Ciphertext[], weights: Ciphertext[], ek: EvaluationKey,
-    progress?: ProgressCallback): Promise<Ciphertext>;
+    progress?: ProgressCallback, options?: TallyWeightedOptions): Promise<Ciphertext>;
+  dotProduct(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension). */
   deviceBuffer(handle: unknown): DeviceBuffer | undefined;
 }
@@ -356,6 +372,11 @@ export declare class NttContext {
    * words; an entry may repeat; out is none of them): one launch (fhe_ct_sum_ptrs). */
   sum(buffers: DeviceBuffer[], out: DeviceBuffer): DeviceBuffer;
   sumAsync(buffers: DeviceBuffer[], out: DeviceBuffer): Promise<DeviceBuffer>;
+  /** out (3 n words) = sum_i multiply(buffersA[i], buffersB[i]) over ciphertexts of 2 n
+   * words; entries may repeat, buffersA[i] may be buffersB[i]; out is none of them: one
+   * fused launch (fhe_ct_dot_ptrs). */
+  dot(buffersA: DeviceBuffer[], buffersB: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): DeviceBuffer;
+  dotAsync(buffersA: DeviceBuffer[], buffersB: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): Promise<DeviceBuffer>;
   ctMultiply(ct1: Words, ct2: Words, out: Words, isNtt?: number): Words;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;

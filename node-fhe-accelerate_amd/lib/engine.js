@@ -672,21 +672,79 @@ function makeEngineClass(native) {
     /** tally_weighted_votes (:1069-1110): multiply + relinearize per ballot
      *  (progress every 100, of 2 * count), then one tally (progress count +
      *  completed of count + (count - 1)) */
-    async tallyWeightedVotes(ballots, weights, ek, progress) {
+    async tallyWeightedVotes(ballots, weights, ek, progress, options) {
       this._check();
       if (!Array.isArray(ballots) || !Array.isArray(weights) || ballots.length !== weights.length) {
         throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
       }
       if (ballots.length === 0) throw new FHEError('Cannot tally empty ballot list', FHEErrorCode.INVALID_PARAMETERS);
+      const mode = options && options.relinearize !== undefined ? options.relinearize : 'each';
+      if (mode !== 'each' && mode !== 'once') {
+        throw new FHEError("options.relinearize must be 'each' or 'once'", FHEErrorCode.INVALID_PARAMETERS);
+      }
       const start = Date.now(), total = ballots.length;
       const report = (current, of) => progress({ stage: 'tally_weighted_votes', current, total: of,
         elapsedMs: Date.now() - start, progressPercent: (current / of) * 100 });
+      if (mode === 'once') {
+        // lazy relinearisation: the fused degree-2 sum, then one key switch.
+        // Same plaintext, less noise; not the words of the per-ballot fold
+        // (the digit decomposition is not linear).  Same progress calls.
+        const r = await this.relinearize(await this.dotProduct(ballots, weights), ek);
+        for (let i = 0; progress && i < total; i++) if ((i + 1) % 100 === 0) report(i + 1, total * 2);
+        for (let i = 1; progress && i < total; i++) report(total + i, total + total - 1);
+        return r;
+      }
       const weighted = [];
       for (let i = 0; i < total; i++) {
         weighted.push(await this.multiplyRelin(ballots[i], weights[i], ek));
         if (progress && (i + 1) % 100 === 0) report(i + 1, total * 2);
       }
       return this.tallyVotes(weighted, progress ? (p) => report(total + p.current, total + p.total) : undefined);
+    }
+    /** Ciphertext inner product sum_i multiply(cts1[i], cts2[i]) as one
+     *  degree-2 ciphertext, in one fused launch (fhe_ct_dot_ptrs); the words
+     *  equal the chain of multiply() and add().  Checks in that chain's
+     *  order (every pair shares cts1[0]'s representation); budget: multiply's
+     *  rule per pair, folded by tallyVotes' tree rule; progress counts the
+     *  pairs. */
+    async dotProduct(cts1, cts2, progress) {
+      this._check();
+      if (!Array.isArray(cts1) || !Array.isArray(cts2) || cts1.length !== cts2.length) {
+        throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (cts1.length === 0) throw new FHEError('Cannot tally empty ballot list', FHEErrorCode.INVALID_PARAMETERS);
+      const start = Date.now(), total = cts1.length;
+      const r = await guard(async () => {
+        const A = [], B = [];
+        const red = Math.log2(this._n) + 5;
+        let level = [], packed = false;
+        for (let i = 0; i < total; i++) {
+          const a = this._rlwe(cts1[i]), b = this._rlwe(cts2[i]);
+          this._sameKey(cts1[i], cts2[i], 'multiply');
+          if (a.comps !== 2 || b.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+          if (i > 0) {
+            this._sameKey(cts1[0], cts1[i], 'add');
+            if (cts1[i].isNtt !== cts1[0].isNtt) throw new FHEError('Cannot combine ciphertexts in different representations (NTT vs coefficient)', FHEErrorCode.INVALID_PARAMETERS);
+          }
+          A.push(a.buf);
+          B.push(b.buf);
+          packed = packed || a.packed || b.packed;
+          level.push(Math.min(cts1[i].noiseBudget, cts2[i].noiseBudget) - red);
+        }
+        while (level.length > 1) {
+          const next = [];
+          for (let i = 0; i + 1 < level.length; i += 2) next.push(Math.min(level[i], level[i + 1]) - 1);
+          if (level.length % 2 === 1) next.push(level[level.length - 1]);
+          level = next;
+        }
+        const out = this._buf(3 * this._n);
+        await this._ctx.dotAsync(A, B, out, !!cts1[0].isNtt);
+        return this._ct(out, cts1[0].keyId, level[0], 2, { packed });
+      });
+      for (let i = 1; progress && i <= total; i++) {
+        progress({ stage: 'dot_product', current: i, total, elapsedMs: Date.now() - start, progressPercent: (i / total) * 100 });
+      }
+      return r;
     }
 
     // ---- multiplicative operations (encryption.cpp:737-980)

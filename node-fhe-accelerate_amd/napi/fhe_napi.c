@@ -930,6 +930,62 @@ static napi_value ctx_sum(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[1], k.argv, 2);
 }
 
+/* dot(buffersA[], buffersB[], out, isNtt?): out = sum_i multiply(A[i], B[i])
+ * (fhe_ct_dot_ptrs), the degree-2 sum in one fused launch.  Every entry is a
+ * DeviceBuffer of this context of 2 n words; entries may repeat and A[i] may
+ * be B[i] (a square); out has 3 n words and is none of them. */
+static int run_dot(job *j) {
+    const uint64_t *const *tab = (const uint64_t *const *)j->owned;
+    return fhe_ct_dot_ptrs(j->c, tab, tab + j->batch, j->batch, (int)j->v[0], 0, j->p[0]);
+}
+static napi_value ctx_dot(napi_env env, napi_callback_info info) {
+    static const char *usage = "dot(buffersA[], buffersB[], out, isNtt?): DeviceBuffers of this context";
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    bool arr_a = false, arr_b = false, is_ntt = false;
+    uint32_t cnt = 0, cnt_b = 0;
+    uint64_t *o;
+    size_t no;
+    if (k.argc < 3 || napi_is_array(env, k.argv[0], &arr_a) != napi_ok || !arr_a ||
+        napi_is_array(env, k.argv[1], &arr_b) != napi_ok || !arr_b ||
+        napi_get_array_length(env, k.argv[0], &cnt) != napi_ok ||
+        napi_get_array_length(env, k.argv[1], &cnt_b) != napi_ok || arr_arg(env, &k, 2, &o, &no) ||
+        k.where != FHE_DEVICE)
+        return bad_args(env, usage), NULL;
+    if (!undef_arg(env, &k, 3) && napi_get_value_bool(env, k.argv[3], &is_ntt) != napi_ok) return bad_args(env, usage), NULL;
+    if (cnt != cnt_b) return range_err(env, "Ballots and weights must have the same size");
+    if (cnt == 0) return range_err(env, "Cannot tally empty ballot list");
+    if (no != 3 * k.n) return range_err(env, "out holds a degree-2 ciphertext (3 polynomials)");
+    uint64_t **tab = (uint64_t **)malloc((size_t)2 * cnt * sizeof *tab);
+    dblock **blks = k.async ? (dblock **)malloc((size_t)2 * cnt * sizeof *blks) : NULL;
+    if (!tab || (k.async && !blks)) {
+        free(tab);
+        free(blks);
+        napi_throw_error(env, "NATIVE_ERROR", "out of memory");
+        return NULL;
+    }
+    for (uint32_t i = 0; i < 2 * cnt; ++i) {
+        napi_value e;
+        dbuf *d = napi_get_element(env, k.argv[i < cnt ? 0 : 1], i < cnt ? i : i - cnt, &e) == napi_ok ? unwrap_buf(env, e) : NULL;
+        if (!d || !d->blk || d->blk->owner != k.k || d->words != 2 * k.n || dbuf_ptr(d) == o) {
+            free(tab);
+            free(blks);
+            return bad_args(env, "dot(buffersA[], buffersB[], out): every entry a DeviceBuffer of 2 n words, none of them out"), NULL;
+        }
+        tab[i] = dbuf_ptr(d);
+        if (blks) blks[i] = d->blk;
+    }
+    job *j = job_new(&k, run_dot, NULL);
+    j->owned = (uint64_t *)tab;
+    j->p[0] = o; j->v[0] = is_ntt ? 1 : 0; j->batch = cnt;
+    if (blks) {  /* pinned like the blocks of arr_arg (job_go) */
+        for (uint32_t i = 0; i < 2 * cnt; ++i) blks[i]->refs++;
+        j->xblks = blks;
+        j->nxblk = (size_t)2 * cnt;
+    }
+    return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+
 /* externalProduct(glwe, ggswCoeff, baseLog, level, out): k = 1, the key
  * prepared per call (host buffers: into host scratch; device: in place of
  * a stream-ordered temporary is not available here, so device callers use
@@ -1528,6 +1584,7 @@ static napi_value init(napi_env env, napi_value exports) {
         M("negate", ctx_negate),
         M("mulScalar", ctx_mul_scalar),
         M("sum", ctx_sum),
+        M("dot", ctx_dot),
         M("forwardMul", ctx_fwd_mul),
         M("externalProduct", ctx_ext_product),
         M("prepareGgsw", ctx_prep_ggsw),
