@@ -8,6 +8,9 @@ Gentleman-Sande + bit-reversal + N^-1), its primitive-root search
 (``findPrimitiveRoot``) and the negacyclic reference of
 ``src/test-utils/homomorphic-multiplication.prop.test.ts:126-189`` / schoolbook
 convolution.  Pure Python ints: only for small cases.
+
+``negacyclic_multiply`` is a third, transform-free route to the ring product
+(one big-integer multiplication), fast enough for n = 16384.
 """
 from __future__ import annotations
 
@@ -100,6 +103,27 @@ def negacyclic_schoolbook(a, b, q):
             else:
                 c[k - n] = (c[k - n] - a[i] * b[j]) % q
     return c
+
+
+def negacyclic_multiply(a, b, q):
+    """a * b mod (X^n + 1, q), exact, by Kronecker substitution: the
+    coefficients (any integers, read mod q) are packed into one Python integer
+    each, in slots wide enough for a coefficient of the plain product
+    (< n (q-1)^2, so 2 bits(q-1) + bits(n) bits, rounded up to bytes); one
+    big-integer product gives the 2n-1 plain coefficients c, and X^n = -1
+    folds them to c[i] - c[i+n].  Shares nothing with the transforms above:
+    no root of unity, no twiddle table, no butterfly."""
+    n = len(a)
+    if len(b) != n:
+        raise ValueError("operand lengths differ")
+    slot = (2 * (q - 1).bit_length() + n.bit_length() + 7) // 8
+
+    def pack(p):
+        return int.from_bytes(b"".join((int(c) % q).to_bytes(slot, "little") for c in p), "little")
+
+    prod = (pack(a) * pack(b)).to_bytes(2 * n * slot, "little")
+    c = [int.from_bytes(prod[i * slot:(i + 1) * slot], "little") for i in range(2 * n)]
+    return [(c[i] - c[i + n]) % q for i in range(n)]
 
 
 def negacyclic_forward(coeffs, q):

@@ -197,6 +197,43 @@ def test_negacyclic_pyref_is_ring_product(golden_dir):
         assert case["product"] == pyref.negacyclic_schoolbook(case["x"], case["y"], q)
 
 
+QG = 18446744069414584321  # 2^64 - 2^32 + 1
+
+
+def _raw_rows(seed, n):
+    """Two rows of raw u64 words with the extremes planted."""
+    rng = np.random.default_rng(seed)
+    a, b = ([int(v) for v in rng.integers(0, 2 ** 64 - 1, n, dtype=np.uint64, endpoint=True)] for _ in range(2))
+    a[0], a[1], a[-1] = 2 ** 64 - 1, 0, 2 ** 64 - 1
+    b[0], b[-1] = 2 ** 64 - 1, 2 ** 64 - 1
+    return a, b
+
+
+@pytest.mark.parametrize("q", [17, P62, QG])
+@pytest.mark.parametrize("n", [8, 64, 256])
+def test_negacyclic_multiply_vs_schoolbook(n, q):
+    """The Kronecker-substitution product against the O(n^2) definition, raw
+    u64 inputs (read mod q), all-(q-1) rows (the largest plain coefficients)
+    and a numpy operand."""
+    a, b = _raw_rows(n + q % 1000, n)
+    assert pyref.negacyclic_multiply(a, b, q) == pyref.negacyclic_schoolbook(a, b, q)
+    top = [q - 1] * n
+    assert pyref.negacyclic_multiply(top, top, q) == pyref.negacyclic_schoolbook(top, top, q)
+    assert pyref.negacyclic_multiply(U(a), U(b), q) == pyref.negacyclic_multiply(a, b, q)
+    one = [1] + [0] * (n - 1)
+    assert pyref.negacyclic_multiply(a, one, q) == [v % q for v in a]
+    x = [0, 1] + [0] * (n - 2)  # times X: the signed shift
+    assert pyref.negacyclic_multiply(a, x, q) == [(-a[-1]) % q] + [v % q for v in a[:-1]]
+
+
+@pytest.mark.parametrize("q", [P62, QG])
+def test_negacyclic_multiply_vs_transform_4096(q):
+    n = 4096
+    a, b = _raw_rows(q % 1000, n)
+    fa, fb = pyref.negacyclic_forward(a, q), pyref.negacyclic_forward(b, q)
+    assert pyref.negacyclic_multiply(a, b, q) == pyref.negacyclic_inverse([x * y % q for x, y in zip(fa, fb)], q)
+
+
 # --------------------------------------------------- fixtures regenerate
 def test_golden_ntt_small(golden_dir):
     for c in load(golden_dir, "ntt_small.json"):
