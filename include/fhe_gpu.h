@@ -310,7 +310,19 @@ int fhe_ct_dot_ptrs(fhe_ctx *ctx, const uint64_t *const *a, const uint64_t *cons
  * fhe_cmux_batch           cmux (:520-540): ct0 + ggsw (x) (ct1 - ct0).
  * fhe_blind_rotate_batch   blind_rotate (:547-577) of acc in place, for each
  *   ciphertext c with its own LWE (lwe_a[c], lwe_b[c]) modulo lwe_q; bsk_ntt
- *   = lwe_dim prepared GGSWs ([lwe_dim][(k+1)*level][k+1][n]).  k = 1 with
+ *   = lwe_dim prepared GGSWs ([lwe_dim][(k+1)*level][k+1][n]).
+ *   Rotation rule (:560, :568): the amount of a word w is
+ *     (int32_t)(uint32_t)((w * 2n + lwe_q / 2) / lwe_q)
+ *   in uint64_t arithmetic: the product wraps at 2^64 and so does the sum
+ *   (near 2^62 a uniform word gives 0..4), and the quotient is truncated to
+ *   its low 32 bits, read as signed.  Mask and body words are used raw, not
+ *   reduced modulo lwe_q; lwe_q need not equal the ring modulus.  acc is
+ *   first multiplied by X^-amount(lwe_b) (a body whose amount is INT32_MIN
+ *   is undefined in the reference); then step i, for amount(lwe_a[i]) = r,
+ *   is skipped when r == 0 (the accumulator keeps its words, raw ones
+ *   included) and otherwise computes acc <- cmux(bsk[i], acc, X^r acc), also
+ *   when r is a non-zero multiple of 2n, where X^r acc = acc and the step
+ *   only reduces the accumulator words below q.  k = 1 with
  *   n <= 16384 runs fused: one launch for the whole loop at n = 512..4096
  *   (two CUs per ciphertext while 16 * ceil(batch / 8) <= CUs, else one;
  *   2 * level CUs at level 2 / 3 while 2 * level * ceil(batch / 8) <= the

@@ -11,6 +11,11 @@ convolution.  Pure Python ints: only for small cases.
 
 ``negacyclic_multiply`` is a third, transform-free route to the ring product
 (one big-integer multiplication), fast enough for n = 16384.
+
+``decompose`` .. ``blind_rotate`` restate the TFHE pieces of BootstrapEngine
+over a ring product passed in, with an explicit LWE modulus: the shared
+reference of the CPU checks of ``ref_cpu.c`` (compat product) and of the GPU
+tests of negacyclic blind rotation (true ring product).
 """
 from __future__ import annotations
 
@@ -169,3 +174,101 @@ def negacyclic_inverse(vals, q):
     ninv = pow(n, -1, q)
     pinv = pow(psi, -1, q)
     return [r[i] * ninv % q * pow(pinv, i, q) % q for i in range(n)]
+
+
+# ---------------------------------------------------------------- TFHE pieces
+# BootstrapEngine's decompose / external_product / rotate_polynomial / cmux /
+# blind_rotate (bootstrap_engine.cpp:122-185, 431-577) restated over Python
+# integers.  The ring product is a parameter ``mul(a, b, q)``: ``polymul``
+# gives the reference's (compat) product inv(fwd(a) . fwd(b)),
+# ``negacyclic_multiply`` the true product mod X^n + 1.  Sums and differences
+# are plain ``% q`` (ModularArithmetic::mod_add / mod_sub reduce their
+# operands first, so they are the same function).  u64 words wrap where the
+# reference's wrap: the rotation amount and the negation of a raw coefficient.
+M64 = (1 << 64) - 1
+
+
+def c_int32_trunc(x):
+    """(int32_t)(uint32_t)x"""
+    x &= 0xFFFFFFFF
+    return x - (1 << 32) if x >> 31 else x
+
+
+def rot_amount(a, n, lwe_q):
+    """blind_rotate's rotation amount (:560): (int32)((a * 2N + lwe_q / 2) /
+    lwe_q) in u64 arithmetic -- the product wraps at 2^64 and so does the
+    sum; a is used raw (not reduced mod lwe_q)."""
+    s = (((int(a) * 2 * n) & M64) + lwe_q // 2) & M64
+    return c_int32_trunc(s // lwe_q)
+
+
+def decompose(poly, q, bl, lv):
+    """decompose (:152-185): signed digits of the raw word, most significant
+    level first, a negative digit d - B stored as q - (B - d)."""
+    base = 1 << bl
+    out = []
+    for l in range(lv):
+        sh = (lv - 1 - l) * bl
+        row = []
+        for c in poly:
+            d = (int(c) >> sh) & (base - 1)
+            row.append((q - (base - d)) % q if d > base // 2 else d)
+        out.append(row)
+    return out
+
+
+def external_product(glwe, ggsw, q, bl, lv, k=1, mul=polymul):
+    """external_product (:431-518): out_j = sum over the rows (i, l) of
+    digit_l(glwe_i) * ggsw[i lv + l][j]; glwe [k+1][n], ggsw [(k+1) lv][k+1][n]."""
+    n = len(glwe[0])
+    res = [[0] * n for _ in range(k + 1)]
+    row = 0
+    for i in range(k + 1):
+        for d in decompose(glwe[i], q, bl, lv):
+            for j in range(k + 1):
+                p = mul(d, [int(v) for v in ggsw[row][j]], q)
+                res[j] = [(a + b) % q for a, b in zip(res[j], p)]
+            row += 1
+    return res
+
+
+def rotate(poly, rot, q):
+    """rotate_polynomial (:122-145): X^rot * poly mod X^n + 1, rot any int32.
+    A coefficient that keeps its sign is copied raw; one that crosses X^n
+    becomes ((q - c) mod 2^64) % q."""
+    n = len(poly)
+    two_n = 2 * n
+    r = c_int32_trunc(rot) % two_n  # same residue as C's ((rot % 2N) + 2N) % 2N
+    out = [0] * n
+    for i, c in enumerate(poly):
+        ni = (i + r) % two_n
+        if ni < n:
+            out[ni] = int(c)
+        else:
+            out[ni - n] = ((q - int(c)) & M64) % q
+    return out
+
+
+def cmux(ggsw, ct0, ct1, q, bl, lv, k=1, mul=polymul):
+    """cmux (:520-540): ct0 + ggsw (x) (ct1 - ct0)."""
+    diff = [[(int(a) - int(b)) % q for a, b in zip(ct1[i], ct0[i])] for i in range(k + 1)]
+    p = external_product(diff, ggsw, q, bl, lv, k, mul)
+    return [[(a + int(b)) % q for a, b in zip(p[i], ct0[i])] for i in range(k + 1)]
+
+
+def blind_rotate(acc, lwe_a, lwe_b, lwe_q, bsk, q, bl, lv, k=1, mul=polymul):
+    """blind_rotate (:547-577): acc <- X^-rot(b) acc, then for every mask word
+    with a non-zero amount acc <- cmux(bsk[i], acc, X^rot(a_i) acc).  Amount
+    0 skips the step (the accumulator keeps its raw words); any other amount,
+    a non-zero multiple of 2N included, computes it."""
+    n = len(acc[0])
+    acc = [[int(v) for v in p] for p in acc]
+    b_rot = -rot_amount(lwe_b, n, lwe_q)
+    acc = [rotate(p, b_rot, q) for p in acc]
+    for i, a in enumerate(lwe_a):
+        a_rot = rot_amount(a, n, lwe_q)
+        if a_rot == 0:
+            continue
+        rot = [rotate(p, a_rot, q) for p in acc]
+        acc = cmux(bsk[i], acc, rot, q, bl, lv, k, mul)
+    return acc

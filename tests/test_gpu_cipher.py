@@ -171,7 +171,10 @@ def test_blind_rotate_vs_oracle(fg, n, q, bl, lv, dim):
     bsk_ntt = be.prepare_ggsw(bsk)
     lwe_a = rnd(62, q, b, dim)
     lwe_a[0, 0] = 0          # rotation 0: the step is skipped
-    lwe_a[0, 1] = q - 1      # rotation 2N: computed (not skipped)
+    # q - 1: rotation 2N, computed (not skipped), while q 2N < 2^64; at P62 the
+    # product wraps and the amount is 0, a second skipped step (the whole
+    # range at 62 bits: test_gpu_blind_rotate_range.py)
+    lwe_a[0, 1] = q - 1
     lwe_a[1, :] = 0          # whole ciphertext skipped
     lwe_b = rnd(63, q, b)
     acc0 = np.zeros((b, k + 1, n), np.uint64)
@@ -211,7 +214,10 @@ def test_blind_rotate_single_launch_matches_step_launches(fg, monkeypatch, n, q,
     bsk = rnd(71 + n, q, dim, (k + 1) * lv, k + 1, n)
     bsk_ntt = be.prepare_ggsw(bsk)
     lwe_a = rnd(72, q, b, dim)
-    lwe_a[0, :3] = [0, q - 1, 1]   # skipped step, rotation 2N, tiny rotation
+    # a skipped step; q - 1: rotation 2N, computed, while q 2N < 2^64 (at the
+    # 60- and 62-bit moduli the product wraps and the amount is 0); 1: amount 0
+    # at every modulus here.  The whole range: test_gpu_blind_rotate_range.py
+    lwe_a[0, :3] = [0, q - 1, 1]
     lwe_a[1, :] = 0                 # all steps skipped
     lwe_b = rnd(73, q, b)
     acc0 = rnd(74, q, b, k + 1, n)  # both components non-zero
@@ -387,7 +393,8 @@ def test_cmux_composed_vs_oracle(fg, n, q, bl, lv, k):
 def test_blind_rotate_composed_vs_oracle(fg, n, q, bl, lv, k, dim):
     """Blind rotation where no fused CMux exists (GLWE dimension k > 1,
     N > 16384): composed steps (X^r acc - acc, composed external product,
-    + acc), bit-exact vs the oracle; skipped steps and a rotation of 2N."""
+    + acc), bit-exact vs the oracle; skipped steps and, at q = 12289, a
+    rotation of 2N."""
     b = 3
     r = fg.PolynomialRing(n, q)
     t = oracle.NTT(n, q)
@@ -396,7 +403,7 @@ def test_blind_rotate_composed_vs_oracle(fg, n, q, bl, lv, k, dim):
     bsk_ntt = be.prepare_ggsw(bsk)
     lwe_a = rnd(n + 32, q, b, dim)
     lwe_a[0, 0] = 0          # rotation 0: the step is skipped
-    lwe_a[0, 1] = q - 1      # rotation 2N: computed
+    lwe_a[0, 1] = q - 1      # rotation 2N, computed, at q = 12289; 0 (skipped) at P62, where the product wraps
     lwe_a[1, :] = 0          # every step skipped
     lwe_b = rnd(n + 33, q, b)
     acc0 = rnd(n + 34, q, b, k + 1, n)

@@ -3,7 +3,9 @@ oracle_ct_multiply, oracle_relinearize, oracle_cmux, oracle_blind_rotate,
 oracle_key_switch) against a second, independently written pure-Python
 restatement of the reference code (encryption.cpp:737-980,
 bootstrap_engine.cpp:122-145, 520-674) built on ``oracle.pyref``'s big-integer
-transform, plus the committed golden vectors.  No GPU needed.
+transform, plus the committed golden vectors.  The TFHE pieces (decompose ..
+blind rotate) are ``oracle.pyref``'s shared restatement, pinned here to the C
+oracle with an LWE modulus of its own.  No GPU needed.
 """
 import json
 import os
@@ -11,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import lwe_inputs as L
 import oracle
 from oracle import pyref
 
@@ -69,70 +72,18 @@ def py_relinearize(ct3, rlk, q, bl, lv):  # encryption.cpp:904-980
     return [r0, r1]
 
 
-def py_decompose(poly, q, bl, lv):  # bootstrap_engine.cpp:152-185
-    base = 1 << bl
-    out = []
-    for l in range(lv):
-        sh = (lv - 1 - l) * bl
-        row = []
-        for c in poly:
-            d = (c >> sh) & (base - 1)
-            row.append((q - (base - d)) % q if d > base // 2 else d)
-        out.append(row)
-    return out
+# decompose / external product / rotate / cmux / blind rotate: the shared
+# restatement in oracle/pyref.py (ring product and LWE modulus as parameters)
+py_rotate = pyref.rotate
 
 
-def py_extprod(glwe, ggsw, q, bl, lv, k=1):  # :431-518
-    n = len(glwe[0])
-    res = [[0] * n for _ in range(k + 1)]
-    row = 0
-    for i in range(k + 1):
-        for d in py_decompose(glwe[i], q, bl, lv):
-            dn = pyref.forward(d, q)
-            for j in range(k + 1):
-                p = pyref.inverse(pw(q, dn, pyref.forward(I(ggsw[row][j]), q)), q)
-                res[j] = [mod_add(q, a, b) for a, b in zip(res[j], p)]
-            row += 1
-    return res
+def py_cmux(ggsw, ct0, ct1, q, bl, lv, k=1):
+    return pyref.cmux(ggsw, ct0, ct1, q, bl, lv, k, pyref.polymul)
 
 
-def py_rotate(poly, rot, q):  # :122-145
-    n = len(poly)
-    two_n = 2 * n
-    r = int(np.int32(rot)) % two_n  # same residue as C's ((rot % 2N) + 2N) % 2N
-    out = [0] * n
-    for i, c in enumerate(poly):
-        ni = (i + r) % two_n
-        if ni < n:
-            out[ni] = c
-        else:
-            out[ni - n] = ((q - c) & M64) % q
-    return out
-
-
-def py_cmux(ggsw, ct0, ct1, q, bl, lv, k=1):  # :520-540
-    diff = [[mod_sub(q, a, b) for a, b in zip(I(ct1[i]), I(ct0[i]))] for i in range(k + 1)]
-    p = py_extprod(diff, ggsw, q, bl, lv, k)
-    return [[mod_add(q, a, b) for a, b in zip(p[i], I(ct0[i]))] for i in range(k + 1)]
-
-
-def c_int32_trunc(x):
-    x &= 0xFFFFFFFF
-    return x - (1 << 32) if x >> 31 else x
-
-
-def py_blind_rotate(acc, lwe_a, lwe_b, bsk, q, bl, lv, k=1):  # :547-577
-    n = len(acc[0])
-    acc = [I(p) for p in acc]
-    b_rot = -c_int32_trunc((((lwe_b * 2 * n) & M64) + q // 2) // q)
-    acc = [py_rotate(p, b_rot, q) for p in acc]
-    for i, a in enumerate(I(lwe_a)):
-        a_rot = c_int32_trunc((((a * 2 * n) & M64) + q // 2) // q)
-        if a_rot == 0:
-            continue
-        rot = [py_rotate(p, a_rot, q) for p in acc]
-        acc = py_cmux(bsk[i], acc, rot, q, bl, lv, k)
-    return acc
+def py_blind_rotate(acc, lwe_a, lwe_b, bsk, q, bl, lv, k=1, lwe_q=None):
+    return pyref.blind_rotate(acc, I(lwe_a), int(lwe_b), q if lwe_q is None else lwe_q, bsk, q, bl, lv, k,
+                              pyref.polymul)
 
 
 def py_key_switch(q, bl, lv, ksk_a, ksk_b, lwe_a, lwe_b):  # :626-674
@@ -198,6 +149,69 @@ def test_blind_rotate_oracle_vs_python(n, q, bl, lv, dim):
     acc[1] = rnd(11, q, n)
     got = t.blind_rotate(1, bl, lv, lwe_a, 37, q, bsk, acc)
     assert [I(r) for r in got] == py_blind_rotate(acc, lwe_a, 37, bsk, q, bl, lv)
+
+
+@pytest.mark.parametrize("n,q,bl,lv,k", [(16, 97, 2, 3, 1), (32, P62, 23, 1, 2), (64, 7681, 63, 1, 1)])
+def test_decompose_and_external_product_oracle_vs_python(n, q, bl, lv, k):
+    t = oracle.NTT(n, q)
+    glwe = rnd(15, q, k + 1, n)
+    glwe[0, :3] = [M64, q, q + 1]  # raw words: the digits are cut from the word as given
+    ggsw = rnd(16, q, (k + 1) * lv, k + 1, n)
+    assert [I(r) for r in oracle.decompose(q, glwe[0], bl, lv)] == pyref.decompose(I(glwe[0]), q, bl, lv)
+    got = t.external_product(k, bl, lv, glwe, ggsw)
+    assert [I(r) for r in got] == pyref.external_product(glwe, ggsw, q, bl, lv, k, pyref.polymul)
+
+
+@pytest.mark.parametrize("lwe_q,a,want", [
+    (97, M64, pyref.c_int32_trunc(((1 << 64) - 128 + 48) // 97)),  # N = 64: 2^64 - 128 + 48 does not wrap ...
+    (257, M64, 0), (1 << 32, M64, 0),  # ... 2^64 - 128 + 128 and + 2^31 do: the SUM wraps as well as the product
+    (256, 255, 128), (256, 1, 1),    # lwe_q = 4N: a tie rounds half up
+    (P62, P62 - 1, 0),               # the product wraps: a uniform word near 2^62 gives 0..4 at most
+    (97, 97 * 5, 5 * 128), (1 << 32, 1 << 56, -(1 << 31)),
+])
+def test_rot_amount_wraps_like_u64(lwe_q, a, want):
+    assert pyref.rot_amount(a, 64, lwe_q) == want
+
+
+@pytest.mark.parametrize("lwe_name", ["2^32", "4N", "257", "P27"])
+@pytest.mark.parametrize("n", [512, 1024, 2048, 4096, 32768])
+def test_planted_masks_reach_every_class(n, lwe_name):
+    """The mask sets of the GPU range tests, at the degrees and sizes they
+    use: every class of step that applies, and more than half of the steps
+    executed.  The old inputs (uniform below a 62-bit lwe_q) fail both."""
+    lwe_q = L.lwe_modulus(lwe_name, n)
+    for b, dim in ((5, 8), (6, 8), (3, 8), (4, 6), (3, 6)):
+        lwe_a = L.masks(60 + b, n, lwe_q, b, dim)
+        L.check_coverage(n, lwe_q, lwe_a)
+        L.bodies(61, n, lwe_q, b)
+    old = rnd(62, P62, 5, 8)
+    old[0, :2], old[1, :] = [0, P62 - 1], 0
+    assert max(max(row) for row in L.amounts(n, P62, old)) <= 4
+    with pytest.raises(AssertionError):
+        L.check_coverage(n, P62, old)
+
+
+@pytest.mark.parametrize("lwe_name", ["2^32", "4N", "257", "P27"])
+@pytest.mark.parametrize("n,q,bl,lv,k", [(64, 7681, 4, 3, 1), (256, P62, 23, 1, 1), (128, P62, 15, 2, 2)])
+def test_blind_rotate_explicit_lwe_modulus_oracle_vs_python(n, q, bl, lv, k, lwe_name):
+    """The generalised restatement (explicit lwe_q, GLWE dimension k, product
+    passed in) against the C oracle, on masks that reach every kind of step:
+    skipped, amounts on both sides of N, exactly 2N, a larger multiple of 2N,
+    a negative int32, raw words (2^64 - 1: the sum wraps), and accumulators
+    holding raw words."""
+    lwe_q = L.lwe_modulus(lwe_name, n)
+    assert lwe_q != q
+    dim, b = 8, 3
+    t = oracle.NTT(n, q)
+    bsk = rnd(50 + n, q, dim, (k + 1) * lv, k + 1, n)
+    lwe_a, lwe_b = L.masks(51, n, lwe_q, b, dim), L.bodies(52, n, lwe_q, b)
+    L.check_coverage(n, lwe_q, lwe_a)
+    assert "negative amount" in L.classes(n, lwe_q, lwe_a)  # planted for every lwe_q here (dim 8)
+    acc0 = rnd(53, q, b, k + 1, n)
+    acc0[0, 0, :3] = acc0[1, 0, :3] = acc0[2, k, :3] = [M64, q, q + 1]  # raw words in the planted rows
+    for i in range(b):
+        got = t.blind_rotate(k, bl, lv, lwe_a[i], int(lwe_b[i]), lwe_q, bsk, acc0[i])
+        assert [I(r) for r in got] == py_blind_rotate(acc0[i], lwe_a[i], lwe_b[i], bsk, q, bl, lv, k, lwe_q), i
 
 
 @pytest.mark.parametrize("q,bl,lv,b", [(P27, 4, 3, 5), (P62, 7, 4, M64 - 2), (97, 2, 4, 0)])
