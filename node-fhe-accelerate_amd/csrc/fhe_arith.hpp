@@ -21,15 +21,19 @@
 namespace FHE_NS {
 
 __device__ __forceinline__ uint32_t mulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
-// 64 x 64 -> high 64.  Variants (lab flag FHE_MULHI64): 0 = __umul64hi (the
-// compiler splits the middle sum into two zero-extended halves: 3 v_mov + a
-// 64-bit add per product); 1/2 = 65-bit middle sum in C (the compiler
-// recomputes the carry with a 64-bit compare); 3 (default) = the carry-out of
-// the v_mad_u64_u32 itself, added with one v_addc.  Measured statically on the
-// q62 C3 kernel (k_ntt_fwd_mul<14, u64>): non-multiply VALU 3180 -> 2763 per
-// wave, multiplies unchanged (1590), no new scratch anywhere.
+// 64 x 64 -> high 64.  FHE_MULHI64 selects the form: 3 (default) takes the
+// carry-out of the middle v_mad_u64_u32 itself and adds it with one v_addc; 4
+// (set by the flag-free units) is carry-free.  Against __umul64hi (the compiler
+// splits the middle sum into two zero-extended halves: 3 v_mov + a 64-bit add
+// per product) form 3 measured statically on the q62 C3 kernel
+// (k_ntt_fwd_mul<14, u64>): non-multiply VALU 3180 -> 2763 per wave, multiplies
+// unchanged (1590), no new scratch anywhere.  A 65-bit middle sum written in C
+// was also tried: the compiler recomputes the carry with a 64-bit compare.
 #ifndef FHE_MULHI64
 #define FHE_MULHI64 3
+#endif
+#if FHE_MULHI64 != 3 && FHE_MULHI64 != 4
+#error "FHE_MULHI64 must be 3 (carry-out form) or 4 (carry-free form)"
 #endif
 __device__ __forceinline__ uint64_t mulhi(uint64_t a, uint64_t b) {
 #if FHE_MULHI64 == 4
@@ -40,7 +44,7 @@ __device__ __forceinline__ uint64_t mulhi(uint64_t a, uint64_t b) {
     const uint64_t m2 = (uint64_t)a0 * b1 + (uint64_t)(uint32_t)m1;
     const uint64_t h = (uint64_t)a1 * b1 + (m1 >> 32);
     return h + (m2 >> 32);
-#elif FHE_MULHI64 == 3
+#else
     // The middle sum x0*b1 + (x1*b0 + hi(x0*b0)) reaches 65 bits: its carry
     // comes out of the v_mad_u64_u32 (SGPR pair) and goes into the high word
     // through one v_addc (s_nop 1: VALU-written SGPR read by a VALU).
@@ -55,20 +59,6 @@ __device__ __forceinline__ uint64_t mulhi(uint64_t a, uint64_t b) {
         : "=v"(hh), "=s"(cy2) : "v"((uint32_t)(h >> 32)), "s"(cy));
     (void)cy2;
     return (uint64_t)(uint32_t)h | ((uint64_t)hh << 32);
-#elif FHE_MULHI64 == 2
-    // middle sum to 65 bits through the carry-out of the 64-bit add
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    const uint64_t m1 = (uint64_t)a1 * b0 + __umulhi(a0, b0);  // < 2^64
-    uint64_t m2;
-    const bool c = __builtin_add_overflow((uint64_t)a0 * b1, m1, &m2);
-    return (uint64_t)a1 * b1 + ((m2 >> 32) | ((uint64_t)c << 32));
-#elif FHE_MULHI64
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    const uint64_t m1 = (uint64_t)a1 * b0 + __umulhi(a0, b0);             // < 2^64
-    const unsigned __int128 m2 = (unsigned __int128)((uint64_t)a0 * b1) + m1;  // < 2^65
-    return (uint64_t)a1 * b1 + (uint64_t)(m2 >> 32);
-#else
-    return __umul64hi(a, b);
 #endif
 }
 // unsigned min: x - k wraps above x when x < k, so min() keeps x.
@@ -91,18 +81,10 @@ __device__ __forceinline__ uint64_t umin(uint64_t a, uint64_t b) { return a < b 
 // measured at full rate (111 lane-ops/CU/clk) where v_bfi_b32 issues at
 // half rate (63; tools/lab/valu_rates.hip, profiles/r6a/valu_rates_ext.txt).
 // Inline asm: written in C, LLVM turns the select of redk64 back into
-// compares and v_cndmask (more, half-rate instructions).  FHE_BFI_ASM=1:
-// the v_bfi_b32 form.
-#ifndef FHE_BFI_ASM
-#define FHE_BFI_ASM 0
-#endif
+// compares and v_cndmask (more, half-rate instructions).
 __device__ __forceinline__ uint32_t bfi32(uint32_t m, uint32_t a, uint32_t b) {
     uint32_t r;
-#if FHE_BFI_ASM
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(a), "v"(b));
-#else
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe4" : "=v"(r) : "v"(a), "v"(b), "v"(m));
-#endif
     return r;
 }
 typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
@@ -123,15 +105,8 @@ __device__ __forceinline__ uint64_t not64(uint64_t x) {
 // A wave-uniform constant the compiler may no longer relate to its source
 // (x + launder(-k) stays a v_lshl_add_u64 instead of being folded back into
 // a borrow-chain subtraction x - k).
-#ifndef FHE_LAUNDER_SGPR
-#define FHE_LAUNDER_SGPR 1
-#endif
 __device__ __forceinline__ uint64_t launder(uint64_t c) {
-#if FHE_LAUNDER_SGPR
     asm("" : "+s"(c));
-#else
-    asm("" : "+r"(c));
-#endif
     return c;
 }
 // x < 2k, k < 2^63: x - k if x >= k else x
@@ -142,18 +117,6 @@ __device__ __forceinline__ uint64_t redk64(uint64_t x, uint64_t k) {
 }
 // a - b + c (mod 2^64) as a + ~b + (c + 1); c + 1 wave-uniform
 __device__ __forceinline__ uint64_t sub_add64(uint64_t a, uint64_t b, uint64_t c1) { return a + not64(b) + c1; }
-
-// Lab flags, off by default: the 64-bit Shoup remainder as one mad chain
-// (Arith::lo_chain64; a further 2763 -> 2561 on the q62 C3 kernel, but 28 more
-// kernels with scratch: negacyclic u64 transforms, k_extprod2, k_dmac), and
-// red2q from the borrow of the subtraction (LLVM rebuilds the compare: no
-// change).
-#ifndef FHE_SHOUP64_CHAIN
-#define FHE_SHOUP64_CHAIN 0
-#endif
-#ifndef FHE_RED64_BORROW
-#define FHE_RED64_BORROW 0
-#endif
 
 // The reference's 64-bit primes, all of the form q = 2^k - d with d < 2^32
 // (parameter_set.cpp:22-42, cpp/tests/test_harness.h:143-147).  A kernel
@@ -175,11 +138,6 @@ template <typename W> struct Tw { W w, wp; };
 template <typename W> struct Scale { Tw<W> a, b; };
 
 // 32-bit forward (CT) twiddle tables hold -w mod 2^32 in Tw::w (Arith::ct).
-#ifndef FHE_NEG_FWD_TW
-#define FHE_NEG_FWD_TW 1
-#endif
-constexpr bool kNegFwdTw = FHE_NEG_FWD_TW;
-
 template <typename W>
 struct Arith {
     W q, q2;      // q, 2q
@@ -190,21 +148,12 @@ struct Arith {
     uint32_t sp;
 
     // x in [0, 2^W): x*w mod q, lazy result in [0, 2q)   (Shoup)
-    template <bool CHAIN = true, int SP = 0>
+    template <int SP = 0>
     __device__ __forceinline__ W shoup(W x, W w, W wp) const {
         W h = mulhi(x, wp);
-#ifndef FHE_SHOUP_MAD
-#define FHE_SHOUP_MAD 1
-#endif
-#ifndef FHE_SHOUP_ASM
-#define FHE_SHOUP_ASM 1
-#endif
-#ifndef FHE_MAD_EARLYCLOBBER
-#define FHE_MAD_EARLYCLOBBER 1
-#endif
-        if constexpr (sizeof(W) == 4 && FHE_SHOUP_ASM) {
-            // One v_mad_u64_u32 for x*w - h*q (mod 2^32): LLVM narrows the
-            // 64-bit form below to two v_mul_lo_u32 + v_sub.  Only the low
+        if constexpr (sizeof(W) == 4) {
+            // One v_mad_u64_u32 for x*w - h*q (mod 2^32), h*(2^32 - q) + x*w:
+            // LLVM narrows the C form to two v_mul_lo_u32 + v_sub.  Only the low
             // half of the addend matters, so its high half is left undefined
             // (no zeroing move).
             typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -214,16 +163,9 @@ struct Arith {
             u32x2 c;
             c.x = x * w;
             uint64_t r, cy;
-#if FHE_MAD_EARLYCLOBBER
             asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(r), "=&s"(cy) : "v"(h), "s"(0u - q), "v"(c));
-#else
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(cy) : "v"(h), "s"(0u - q), "v"(c));
-#endif
             (void)cy;
             return (W)r;
-        } else if constexpr (sizeof(W) == 4 && FHE_SHOUP_MAD) {
-            // x*w - h*q (mod 2^32) as one v_mad_u64_u32: h*(2^32 - q) + x*w
-            return (W)((uint64_t)h * (uint32_t)(0u - q) + (uint32_t)(x * w));
         } else if constexpr (sizeof(W) == 8 && SP != 0) {
             // q = 2^k - d (kSparsePrimes[SP]): -(h q) = h d - (h << k) =
             // h0 d + ((h1 d - (h0 << (k - 32))) << 32)  (mod 2^64)
@@ -237,59 +179,14 @@ struct Arith {
             (void)cy;
             const uint32_t ph = (uint32_t)(P >> 32) + h1 * d - (h0 << sk);
             return x * w + pair64((uint32_t)P, ph);
-        } else if constexpr (sizeof(W) == 8 && FHE_SHOUP64_CHAIN && CHAIN) {
-            return (W)lo_chain64(x, w, h);
         } else if constexpr (sizeof(W) == 8 && FHE_U64_NOVCC) {
             return x * w + h * (W)launder(W(0) - q);  // two low products and one v_lshl_add_u64: no borrow
         } else {
             return x * w - h * q;
         }
     }
-    // 64-bit x*w - h*q (mod 2^64) as x*w + h*(2^64 - q): six v_mad_u64_u32
-    // and no subtraction.  The two low-word products go through the 64-bit
-    // adder of the mad; the four cross products only feed the high word, so
-    // they accumulate in the low half of a mad (one instruction each instead
-    // of v_mul_lo + v_add3 + the borrow chain of a 64-bit subtract).
-    __device__ __forceinline__ uint64_t lo_chain64(uint64_t x, uint64_t w, uint64_t h) const {
-        const uint64_t nq = 0ull - (uint64_t)q;
-        const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32), w0 = (uint32_t)w, w1 = (uint32_t)(w >> 32);
-        const uint32_t h0 = (uint32_t)h, h1 = (uint32_t)(h >> 32);
-        const uint32_t n0 = (uint32_t)nq, n1 = (uint32_t)(nq >> 32);
-        uint64_t p = (uint64_t)x0 * w0;
-        p = (uint64_t)h0 * n0 + p;
-        uint32_t acc = madlo(x0, w1, (uint32_t)(p >> 32));
-        acc = madlo(x1, w0, acc);
-        acc = madlo_s(h0, n1, acc);
-        acc = madlo_s(h1, n0, acc);
-        return (uint64_t)(uint32_t)p | ((uint64_t)acc << 32);
-    }
-    // a*b + c (mod 2^32) in one v_mad_u64_u32 (high half of the addend and
-    // of the result unused); _s: b wave-uniform.
-    static __device__ __forceinline__ uint32_t madlo(uint32_t a, uint32_t b, uint32_t c) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        u32x2 cc;
-        cc.x = c;
-        uint64_t r, cy;
-        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(r), "=&s"(cy) : "v"(a), "v"(b), "v"(cc));
-        (void)cy;
-        return (uint32_t)r;
-    }
-    static __device__ __forceinline__ uint32_t madlo_s(uint32_t a, uint32_t b, uint32_t c) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        u32x2 cc;
-        cc.x = c;
-        uint64_t r, cy;
-        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(r), "=&s"(cy) : "v"(a), "s"(b), "v"(cc));
-        (void)cy;
-        return (uint32_t)r;
-    }
     template <int SP = 0>
-    __device__ __forceinline__ W shoup(W x, Tw<W> t) const { return shoup<true, SP>(x, t.w, t.wp); }
-    // Inverse butterflies keep the plain 64-bit form: with the mad chain the
-    // compiler gives the non-negacyclic u64 inverse kernels a 256-byte stack
-    // frame (k_ntt_inv / k_polymul <14, u64>).
-    template <int SP = 0>
-    __device__ __forceinline__ W shoup_inv(W x, Tw<W> t) const { return shoup<false, SP>(x, t.w, t.wp); }
+    __device__ __forceinline__ W shoup(W x, Tw<W> t) const { return shoup<SP>(x, t.w, t.wp); }
 
     // Montgomery: a*b*R^-1 mod q in [0, 2q); requires a*b < q*R.
     // 64-bit words (FHE_U64_NOVCC): the signed form (a*b - m*q) / R + q with
@@ -314,19 +211,16 @@ struct Arith {
     static __device__ __forceinline__ W redk(W x, W k) {
         if constexpr (sizeof(W) == 8 && FHE_U64_NOVCC) {
             return (W)redk64(x, k);
-        } else if constexpr (sizeof(W) == 8 && FHE_RED64_BORROW) {
-            W d;
-            return __builtin_sub_overflow(x, k, &d) ? x : d;
         } else {
             return umin(x, W(x - k));
         }
     }
     __device__ __forceinline__ W canon4(W x) const { return red1q(red2q(x)); }     // [0,4q)->[0,q)
 
-    // 32-bit forward twiddles are stored negated, {-w mod 2^32, w'}
-    // (kNegFwdTw): one v_mad_u64_u32 then yields nb = h*q - y*w = -b (mod
-    // 2^32), and the butterfly is x - nb, x + nb + 2q: a v_sub and a v_add3
-    // instead of an add, a sub and an add.
+    // 32-bit forward twiddles are stored negated, {-w mod 2^32, w'}: one
+    // v_mad_u64_u32 then yields nb = h*q - y*w = -b (mod 2^32), and the
+    // butterfly is x - nb, x + nb + 2q: a v_sub and a v_add3 instead of an
+    // add, a sub and an add.
     __device__ __forceinline__ W shoup_neg(W y, Tw<W> t) const {
         const W h = mulhi(y, t.wp);
         typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -341,7 +235,7 @@ struct Arith {
     template <int SP = 0>
     __device__ __forceinline__ void ct(W &x, W &y, Tw<W> t) const {
         W a = red2q(x);
-        if constexpr (sizeof(W) == 4 && FHE_NEG_FWD_TW) {
+        if constexpr (sizeof(W) == 4) {
             const W nb = shoup_neg(y, t);
             x = a - nb;
             y = a + nb + q2;
@@ -360,7 +254,7 @@ struct Arith {
     template <int SP = 0>
     __device__ __forceinline__ void ct_lazy(W &x, W &y, Tw<W> t) const {
         W a = x;
-        if constexpr (sizeof(W) == 4 && FHE_NEG_FWD_TW) {
+        if constexpr (sizeof(W) == 4) {
             const W nb = shoup_neg(y, t);
             x = a - nb;
             y = a + nb + q2;
@@ -399,15 +293,15 @@ struct Arith {
         W s = x + y;
         W d = sub2q(x, y);
         x = red2q(s);
-        y = shoup_inv<SP>(d, t);
+        y = shoup<SP>(d, t);
     }
     // Last GS stage with the N^-1 scaling folded in (w = 1 at stage 0).
     template <int SP = 0>
     __device__ __forceinline__ void gs_scaled(W &x, W &y, Scale<W> ninv) const {
         W s = x + y;
         W d = sub2q(x, y);
-        x = shoup_inv<SP>(s, ninv.a);
-        y = shoup_inv<SP>(d, ninv.b);
+        x = shoup<SP>(s, ninv.a);
+        y = shoup<SP>(d, ninv.b);
     }
 };
 

@@ -61,19 +61,10 @@ struct BrArgs {
 // below: the transforms are throughput-bound on the one CU, and 16 per thread
 // (half the waves) measured 31.2 vs 20.7 ms (N = 2048, L = 2) and 70.7 vs
 // 58.6 ms (N = 4096, L = 3) per batch-64 blind rotation (round 4).
-#ifndef FHE_BR_LOGE
-#define FHE_BR_LOGE 3
-#endif
-#ifndef FHE_BR_XACC
-#define FHE_BR_XACC 1
-#endif
-#ifndef FHE_BR_LOGE_SMALL
-#define FHE_BR_LOGE_SMALL FHE_BR_LOGE
-#endif
 template <int LOGN>
 constexpr int br_key() {  // LOGN may carry key bits (gk_compat)
     constexpr int L = gk_logn(LOGN);
-    return L >= 12 ? gk(LOGN, FHE_BR_LOGE) : gk(LOGN, L - 7 < FHE_BR_LOGE_SMALL ? L - 7 : FHE_BR_LOGE_SMALL);
+    return gk(LOGN, L - 7 < 3 ? L - 7 : 3);
 }
 template <int LOGN>
 constexpr int br_threads() { return 2 * Geo<br_key<LOGN>()>::T; }
@@ -97,7 +88,7 @@ __global__ void __launch_bounds__(br_threads<LOGN>()) k_br_persist(BrArgs D, Ntt
     constexpr bool CV = G::E <= 8 && THREADS <= 512;
     // the other half's MAC terms summed over the levels in VGPRs and
     // exchanged once per step (else once per level through LDS)
-    constexpr bool XACC = FHE_BR_XACC && G::E <= 8 && (THREADS <= 512 || FHE_BR_XACC == 2);
+    constexpr bool XACC = G::E <= 8 && THREADS <= 512;
     static_assert(G::LW >= G::N, "cross terms fit an exchange region");
     constexpr int N = G::N;
     __shared__ uint64_t accs[2][N];   // raw accumulators (component j)
@@ -257,7 +248,7 @@ __device__ __forceinline__ void fwd_rest_lb(W *lds, W (&v)[LB][Geo<LOGN>::E], ui
         load_tw<LOGN, PASS, W, 0, PF>(tau, tw, t);  // in flight across the exchange
 #pragma unroll
         for (int l = 0; l < LB; ++l) lds_store<LOGN, PASS - 1>(lds + l * G::LW, v[l], tau);
-        xbar<lab_local<PASS - 1, PASS>()>();
+        __syncthreads();
 #pragma unroll
         for (int l = 0; l < LB; ++l) lds_load<LOGN, PASS>(lds + l * G::LW, v[l], tau);
         load_tw<LOGN, PASS, W, PF, 8>(tau, tw, t);
@@ -303,11 +294,6 @@ __device__ __forceinline__ u64x2v pair128(uint64_t a, uint64_t b) {
     v.y = b;
     return v;
 }
-// 1: the hand-off payload as 16-byte sc1 stores / loads (lane-contiguous
-// word pairs); 0: 8-byte agent-scope atomics at the words' own positions
-#ifndef FHE_BR_PAIR_X16
-#define FHE_BR_PAIR_X16 1
-#endif
 struct BrPairX {
     uint32_t *flag;     // [batch][2] executed-step epochs (zeroed before each launch)
     uint32_t *fail;     // [batch] set by a workgroup that gave up (zeroed before each launch)
@@ -316,38 +302,24 @@ struct BrPairX {
     uint64_t *stamps = nullptr;  // lab stamp build only: [grid][8] phase cycle sums
 };
 constexpr uint32_t kBrAbort = 0x80000000u;
-// Flag store / poll memory order.  0: relaxed agent-scope atomics ordered by
-// the drained write-through payload (the MICROARCH "sc1" form); 1: the flag
-// stored with release and polled with acquire semantics (agent scope) -- the
-// formal HIP memory-model form, which adds an L2 write-back per step.
-#ifndef FHE_BR_PAIR_ACQREL
-#define FHE_BR_PAIR_ACQREL 0
-#endif
+// Flag store / poll memory order: relaxed agent-scope atomics ordered by the
+// drained write-through payload (the MICROARCH "sc1" form).  Release / acquire
+// on the flag (the formal HIP memory-model form) adds an L2 write-back per step.
 // 4 coefficients per thread (N / 4 threads per workgroup): 12.0 / 29.6 ms for
 // the two presets and 4.3 ms for 64 ciphertexts at N = 1024, vs 14.0 / 31.9 /
 // 6.1 ms at 8 per thread (round 4).
-#ifndef FHE_BR_PAIR_LOGE
-#define FHE_BR_PAIR_LOGE 2
-#endif
-#ifndef FHE_BR_PAIR_LOGE_SMALL
-#define FHE_BR_PAIR_LOGE_SMALL 2
-#endif
 template <int LOGN>
-constexpr int br_pair_key() { return gk(LOGN, gk_logn(LOGN) >= 12 ? FHE_BR_PAIR_LOGE : FHE_BR_PAIR_LOGE_SMALL); }
+constexpr int br_pair_key() { return gk(LOGN, 2); }
 // Levels transformed in lockstep: up to 4, as many LDS exchange regions as
 // fit beside the accumulator (tfhe-256-secure, N = 4096 with 64-bit words:
 // 3 = its whole L).  Levels beyond LB run in further chunks of LB.
-#ifndef FHE_BR_PAIR_LB
-#define FHE_BR_PAIR_LB 4
-#endif
 template <int LOGN, typename W>
 constexpr int br_pair_lb() {
     using G = Geo<br_pair_key<LOGN>()>;
     // 128 VGPRs at 16 waves: LB = 4 spills; LB = 3 with 64-bit words spills
     // 4 VGPRs and still measured 29.6 vs 31.0 ms (LB = 1) at
     // tfhe-256-secure (round 5)
-    const int cap = G::T >= 1024 ? 3 : 4;
-    int lb = FHE_BR_PAIR_LB < cap ? FHE_BR_PAIR_LB : cap;
+    int lb = G::T >= 1024 ? 3 : 4;
     while (lb > 1 && G::N * 8 + lb * G::LW * (int)sizeof(W) > 150 * 1024) --lb;
     return lb;
 }
@@ -395,6 +367,7 @@ __global__ void __launch_bounds__(Geo<br_pair_key<LOGN>()>::T) k_br_pair(BrArgs 
     using G = Geo<K>;
     constexpr int N = G::N, T = G::T;
     constexpr bool CV = G::E <= 8;
+    static_assert(G::E == 4, "the hand-off moves two 16-byte words per lane");
     __shared__ uint64_t acc[N];      // raw accumulator component h
     __shared__ W lds[LB * G::LW];    // NTT exchange, one region per lockstep level
     __shared__ uint32_t fail;
@@ -507,40 +480,32 @@ __global__ void __launch_bounds__(Geo<br_pair_key<LOGN>()>::T) k_br_pair(BrArgs 
         {
             uint32_t tx = tau;
             asm volatile("" : "+v"(tx));
-            if constexpr (FHE_BR_PAIR_X16 && G::E >= 2 && G::E <= 8) {
-                // 16-byte sc1 stores, lane-contiguous pairs (the partner's lane
-                // tau reads exactly these words).  The s_nop 1 inside the asm:
-                // a store of more than 8 bytes reads its data VGPRs after
-                // issue, and the compiler's next VALU may already overwrite
-                // them (its hazard pass does not pad inline asm) -- without it
-                // a partner received an address word instead of a MAC term
-                // now and then (round 6: the intermittent pair-vs-step test
-                // failure at N = 2048, and every 64-bit k_br_multi result)
+            // 16-byte sc1 stores, lane-contiguous pairs (the partner's lane
+            // tau reads exactly these words; 8-byte agent-scope atomics at the
+            // words' own positions were the earlier form).  The s_nop 1 inside
+            // the asm: a store of more than 8 bytes reads its data VGPRs after
+            // issue, and the compiler's next VALU may already overwrite them
+            // (its hazard pass does not pad inline asm) -- without it a
+            // partner received an address word instead of a MAC term now and
+            // then (round 6: the intermittent pair-vs-step test failure at
+            // N = 2048, and every 64-bit k_br_multi result)
 #pragma unroll
-                for (int e = 0; e < G::E; e += 2) {
-                    g64 *p = mybuf + par + 2 * ((e / 2) * T + tx);
-                    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(pair128((uint64_t)xacc[e], (uint64_t)xacc[e + 1]))
-                                 : "memory");
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < G::E; ++e)
-                    __hip_atomic_store(mybuf + par + gidx<K, G::NP - 1>(tx, e), (uint64_t)xacc[e], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
+            for (int e = 0; e < G::E; e += 2) {
+                g64 *p = mybuf + par + 2 * ((e / 2) * T + tx);
+                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(pair128((uint64_t)xacc[e], (uint64_t)xacc[e + 1]))
+                             : "memory");
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains
         __syncthreads();
         BR_STAMP(3);
         if (tau == 0)
-            __hip_atomic_store(myflag, epoch, FHE_BR_PAIR_ACQREL ? __ATOMIC_RELEASE : __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(myflag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (tau < 64) {  // wave 0 polls the partner's flag, for at most X.timeout
             const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
             bool ok = false;
             for (;;) {
-                const uint32_t f = __hip_atomic_load(peerflag, FHE_BR_PAIR_ACQREL ? __ATOMIC_ACQUIRE : __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
+                const uint32_t f = __hip_atomic_load(peerflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (f & kBrAbort) break;  // the partner gave up
                 if (f >= epoch && X.timeout != 0) {  // zero budget: the test's never-answering partner
                     ok = true;
@@ -561,38 +526,20 @@ __global__ void __launch_bounds__(Geo<br_pair_key<LOGN>()>::T) k_br_pair(BrArgs 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // keeps the payload loads below the poll
         uint32_t ti = tau;
         asm volatile("" : "+v"(ti));
-        if constexpr (FHE_BR_PAIR_X16 && G::E >= 2 && G::E <= 8) {
+        {
             // the loads and their wait in ONE asm statement: the outputs exist
             // for the compiler only once they have landed (an output the
             // compiler spills between a load and a separate wait would be
             // stored before it arrives)
             u64x2v x[G::E / 2];
             const g64 *p0 = peerbuf + par + 2 * ti;
-            if constexpr (G::E == 2) {
-                asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(x[0]) : "v"(p0) : "memory");
-            } else if constexpr (G::E == 4) {
-                asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\t"
-                             "s_waitcnt vmcnt(0)"
-                             : "=&v"(x[0]), "=&v"(x[1]) : "v"(p0), "v"(p0 + 2 * T) : "memory");
-            } else {
-                static_assert(G::E == 8, "2, 4 or 8 words per lane");
-                asm volatile("global_load_dwordx4 %0, %4, off sc1\n\tglobal_load_dwordx4 %1, %5, off sc1\n\t"
-                             "global_load_dwordx4 %2, %6, off sc1\n\tglobal_load_dwordx4 %3, %7, off sc1\n\t"
-                             "s_waitcnt vmcnt(0)"
-                             : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3])
-                             : "v"(p0), "v"(p0 + 2 * T), "v"(p0 + 4 * T), "v"(p0 + 6 * T) : "memory");
-            }
+            asm volatile("global_load_dwordx4 %0, %2, off sc1\n\tglobal_load_dwordx4 %1, %3, off sc1\n\t"
+                         "s_waitcnt vmcnt(0)"
+                         : "=&v"(x[0]), "=&v"(x[1]) : "v"(p0), "v"(p0 + 2 * T) : "memory");
 #pragma unroll
             for (int e = 0; e < G::E; e += 2) {
                 oacc[e] = A.ar.red2q(oacc[e] + (W)x[e / 2].x);
                 oacc[e + 1] = A.ar.red2q(oacc[e + 1] + (W)x[e / 2].y);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < G::E; ++e) {
-                const W x = (W)__hip_atomic_load(peerbuf + par + gidx<K, G::NP - 1>(ti, e), __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-                oacc[e] = A.ar.red2q(oacc[e] + x);
             }
         }
         BR_STAMP(5);
@@ -627,18 +574,13 @@ __global__ void __launch_bounds__(Geo<br_pair_key<LOGN>()>::T) k_br_pair(BrArgs 
 // ABORT + fail[] + the host's repair pass when a partner does not answer).
 // The M workgroups of a ciphertext are blocks b, b + 8, ..., b + 8 (M - 1):
 // one XCD.  Payload per (ciphertext, member): [2 parities][2 components][N].
-// Dense form (DN): two workgroups per CU (8 coefficients per thread, no LDS
-// pad), for batches whose M workgroups per ciphertext exceed one per CU.
-template <int LOGN, bool DN>
-constexpr int br_multi_key() { return DN ? gk(LOGN, 3) : br_pair_key<LOGN>(); }
-template <int LOGN, bool DN>
-constexpr int br_multi_threads() { return Geo<br_multi_key<LOGN, DN>()>::T; }
-template <int LOGN, bool DN>
-constexpr int br_multi_waves() { return DN ? 2 * br_multi_threads<LOGN, DN>() / 256 : 1; }
-template <int LOGN, typename W, int M, bool DN>
-__global__ void __launch_bounds__((br_multi_threads<LOGN, DN>()), (br_multi_waves<LOGN, DN>()))
+// Geometry and LDS pad of k_br_pair (one workgroup per CU).
+template <int LOGN>
+constexpr int br_multi_threads() { return Geo<br_pair_key<LOGN>()>::T; }
+template <int LOGN, typename W, int M>
+__global__ void __launch_bounds__((br_multi_threads<LOGN>()), 1)
     k_br_multi(BrArgs D, NttArgs<W> A, BrPairX X, uint32_t batch) {
-    constexpr int K = br_multi_key<LOGN, DN>();
+    constexpr int K = br_pair_key<LOGN>();
     using G = Geo<K>;
     constexpr int N = G::N, T = G::T, L = M / 2;
     static_assert(M == 4 || M == 6, "two or three digit levels");
@@ -711,14 +653,11 @@ __global__ void __launch_bounds__((br_multi_threads<LOGN, DN>()), (br_multi_wave
                 xacc[e] = A.ar.mont(v[0][e], (W)kv[1][e]);
             }
         }
-#ifndef FHE_BR_MULTI_INVPF
-#define FHE_BR_MULTI_INVPF 1
-#endif
         // the inverse's first-pass twiddles, in flight across the hand-off
         // (inv_poly_from_regs would load them after it)
         constexpr int LAST = G::NP - 1;
         Tw<W> tl[PassTw<K, LAST>::COUNT];
-        if constexpr (FHE_BR_MULTI_INVPF) load_tw<K, LAST>(tau, A.twi, tl);
+        load_tw<K, LAST>(tau, A.twi, tl);
         ++epoch;
         const uint32_t par = (epoch & 1) * 2 * N;
         {
@@ -777,22 +716,15 @@ __global__ void __launch_bounds__((br_multi_threads<LOGN, DN>()), (br_multi_wave
             }
         }
         // component h: inverse, then acc_h = mod_add(inv, red_q(acc_h))
-        if constexpr (FHE_BR_MULTI_INVPF && !stream_tw<K, W>()) {
-            inv_pass<K, LAST, true>(oacc, tl, A.ar, A.ninv);
-            inv_rest<K, LAST - 1, true, kPfSingle>(lds, oacc, ti, A.twi, A.ar, A.ninv);
+        // (inv_poly_from_regs with the last pass's twiddles already loaded)
+        static_assert(!stream_tw<K, W>(), "whole-pass twiddles");
+        inv_pass<K, LAST, true>(oacc, tl, A.ar, A.ninv);
+        inv_rest<K, LAST - 1, true, kPfSingle>(lds, oacc, ti, A.twi, A.ar, A.ninv);
 #pragma unroll
-            for (int t = 0; t < G::E; ++t) {
-                const uint32_t gi = ti + cbrv(t, G::LOGE) * T;
-                const uint64_t a = acc[gi];
-                acc[gi] = addq((uint64_t)A.ar.red1q(oacc[t]), canon ? a : red_q(a, q, mu), q);
-            }
-        } else {
-            inv_poly_from_regs<K, kPfSingle, false>(lds, oacc, ti, nullptr, true, A, A.ninv, 0,
-                                                    [&](uint32_t gi, uint64_t x) -> uint64_t {
-                                                        const uint64_t a = acc[gi];
-                                                        acc[gi] = addq(x, canon ? a : red_q(a, q, mu), q);
-                                                        return 0;
-                                                    });
+        for (int t = 0; t < G::E; ++t) {
+            const uint32_t gi = ti + cbrv(t, G::LOGE) * T;
+            const uint64_t a = acc[gi];
+            acc[gi] = addq((uint64_t)A.ar.red1q(oacc[t]), canon ? a : red_q(a, q, mu), q);
         }
         __syncthreads();
         canon = true;
@@ -816,11 +748,8 @@ __global__ void __launch_bounds__((br_multi_threads<LOGN, DN>()), (br_multi_wave
 // 2^LOGP transforms at a time (groups of 256 >> LOGP threads).  Four groups
 // (fewer, longer rounds: 2 forward and 1 inverse round per step at K1 L = 6
 // instead of 3 and 2) measured slower on MI355X -- 25.2 vs 20.1 ms for one
-// k = 2, N = 1024 blind rotation (profiles/r3j) -- so two (FHE_BRK_P4=1
-// keeps the four-group build for A/B).
-#ifndef FHE_BRK_P4
-#define FHE_BRK_P4 0
-#endif
+// k = 2, N = 1024 blind rotation (profiles/r3j) -- so two.
+constexpr int kBrKLogP = 1;
 template <int LOGN, int LOGP>
 constexpr int br_k_key() { return gk(LOGN, LOGN - 8 + LOGP); }
 template <int LOGN, typename W, int K1, int LOGP>
@@ -828,12 +757,8 @@ constexpr int br_k_lds_bytes() {
     using G = Geo<br_k_key<LOGN, LOGP>()>;
     return K1 * G::N * 8 + (1 << LOGP) * G::LW * (int)sizeof(W) + (1 << LOGP) * K1 * G::N * (int)sizeof(W);
 }
-template <int LOGN, typename W, int K1>
-constexpr int br_k_logp() { return FHE_BRK_P4 && br_k_lds_bytes<LOGN, W, K1, 2>() <= 160 * 1024 ? 2 : 1; }
 // twiddle stages issued ahead in the k >= 2 kernel's transforms
-#ifndef FHE_BRK_PF
-#define FHE_BRK_PF 4
-#endif
+constexpr int kBrKPf = 4;
 template <int LOGN, typename W, int K1, int LOGP>
 __global__ void __launch_bounds__(256) k_br_persist_k(BrArgs D, NttArgs<W> A) {
     constexpr int K = br_k_key<LOGN, LOGP>();
@@ -897,7 +822,7 @@ __global__ void __launch_bounds__(256) k_br_persist_k(BrArgs D, NttArgs<W> A) {
                 return d;
             });
             fwd_pass<K, 0, false>(v, t0, A.ar);
-            fwd_rest<K, 1, false, FHE_BRK_PF>(lds, v, tr, A.twf, A.ar);
+            fwd_rest<K, 1, false, kBrKPf>(lds, v, tr, A.twf, A.ar);
             if (active) {
                 // raw output (< 4q) times canonical keys: valid Montgomery pairs
 #pragma unroll
@@ -933,7 +858,7 @@ __global__ void __launch_bounds__(256) k_br_persist_k(BrArgs D, NttArgs<W> A) {
                 v[e] = x;
             }
             uint64_t *ap = accs[active ? j : 0];
-            inv_poly_from_regs<K, FHE_BRK_PF, false>(lds, v, ti, nullptr, true, A, A.ninv, 0,
+            inv_poly_from_regs<K, kBrKPf, false>(lds, v, ti, nullptr, true, A, A.ninv, 0,
                                                      [&](uint32_t gi, uint64_t x) -> uint64_t {
                                                          if (active) ap[gi] = addq(x, red_q(ap[gi], q, mu), q);
                                                         return 0;
@@ -951,7 +876,7 @@ __global__ void __launch_bounds__(256) k_br_persist_k(BrArgs D, NttArgs<W> A) {
 constexpr int kBrK1Max = 5;
 template <int LOGN, typename W, int K1>
 constexpr bool brk_fits() {
-    return LOGN >= 9 && LOGN <= 11 && br_k_lds_bytes<LOGN, W, K1, br_k_logp<LOGN, W, K1>()>() <= 160 * 1024;
+    return LOGN >= 9 && LOGN <= 11 && br_k_lds_bytes<LOGN, W, K1, kBrKLogP>() <= 160 * 1024;
 }
 template <int LOGN, typename W>
 static bool brk_fits_rt(int k1) {
@@ -977,8 +902,7 @@ bool br_persist_supported(const Plan &p, int k1) {
 template <int LOGN, typename W, int K1>
 static hipError_t brk_launch(const Plan &p, const BrArgs &D, size_t batch, const NttArgs<W> &A) {
     if constexpr (brk_fits<LOGN, W, K1>()) {
-        constexpr int LP = br_k_logp<LOGN, W, K1>();
-        hipLaunchKernelGGL((k_br_persist_k<LOGN, W, K1, LP>), dim3((unsigned)batch), dim3(256), 0, p.stream, D, A);
+        hipLaunchKernelGGL((k_br_persist_k<LOGN, W, K1, kBrKLogP>), dim3((unsigned)batch), dim3(256), 0, p.stream, D, A);
         return hipGetLastError();
     } else {
         return hipErrorInvalidValue;
@@ -1034,21 +958,15 @@ bool br_pair_supported(const Plan &p, int k1, size_t batch) {
 }
 // M = 2 level CUs per ciphertext (k_br_multi) when every ciphertext's M
 // workgroups fit one XCD beside the others dealt to it: 8 ceil(batch / 8)
-// ciphertexts' worth of blocks, M ceil(batch / 8) per XCD, one per CU; up to
-// twice that in the dense form (two per CU, kBrMultiDense bit); 0 = the pair.
-// (The dense form measured slower than the pair: tfhe-256-secure at batch 64
-// 32.6 vs 28.2 ms, round 6, profiles/r6r; lab FHE_BR_MULTI_DENSE=1, parity
-// green in the blind-rotation suite.)
-#ifndef FHE_BR_MULTI_DENSE
-#define FHE_BR_MULTI_DENSE 0
-#endif
-constexpr int kBrMultiDense = 0x100;
+// ciphertexts' worth of blocks, M ceil(batch / 8) per XCD, one per CU; 0 = the
+// pair.  (Two workgroups per CU at 8 coefficients per thread, for up to twice
+// that batch, measured slower than the pair: tfhe-256-secure at batch 64 32.6
+// vs 28.2 ms, round 6, profiles/r6r.)
 int br_multi_members(const Plan &p, int level, size_t batch) {
     if (p.wide || level < 2 || level > 3 || p.logn < 10 || p.logn > 12 || batch == 0) return 0;
     const int M = 2 * level;
     const size_t per_xcd = (size_t)M * ((batch + 7) / 8), cus = (size_t)p.cus / 8;
-    if (per_xcd <= cus) return M;
-    return FHE_BR_MULTI_DENSE && per_xcd <= 2 * cus ? (M | kBrMultiDense) : 0;
+    return per_xcd <= cus ? M : 0;
 }
 // scratch: flags [batch][M] u32 + fail [batch] u32 (16-byte aligned), the
 // saved input accumulators [batch][2][N], the hand-off buffers
@@ -1058,7 +976,7 @@ static size_t br_pair_flag_bytes(size_t batch, int members) {
 }
 size_t br_pair_scratch_bytes(const Plan &p, size_t batch, int level, bool multi) {
     const size_t n = (size_t)1 << p.logn;
-    const int M = multi ? br_multi_members(p, level, batch) & 0xff : 0;
+    const int M = multi ? br_multi_members(p, level, batch) : 0;
     const size_t xbuf = M ? batch * M * 4 * n * 8 : batch * 2 * 2 * n * 8;
     return br_pair_flag_bytes(batch, M ? M : 2) + batch * 2 * n * 8 + xbuf;
 }
@@ -1083,12 +1001,12 @@ static hipError_t br_pair_lb_one(const Plan &p, const BrArgs &D, const BrPairX &
     return hipLaunchCooperativeKernel((const void *)k_br_pair<LOGN, W, LB>, dim3(grid), block, args, PAD,
                                       p.stream);
 }
-template <int LOGN, typename W, int M, bool DN>
+template <int LOGN, typename W, int M>
 static hipError_t br_multi_one(const Plan &p, const BrArgs &D, const BrPairX &X, size_t batch, const NttArgs<W> &A) {
-    constexpr int PAD = DN ? 0 : br_pair_pad_lds<LOGN, W, 1>();
+    constexpr int PAD = br_pair_pad_lds<LOGN, W, 1>();
     const unsigned grid = (unsigned)(8 * M * ((batch + 7) / 8));
-    hipLaunchKernelGGL((k_br_multi<LOGN, W, M, DN>), dim3(grid), dim3(br_multi_threads<LOGN, DN>()), PAD,
-                       p.stream, D, A, X, (uint32_t)batch);
+    hipLaunchKernelGGL((k_br_multi<LOGN, W, M>), dim3(grid), dim3(br_multi_threads<LOGN>()), PAD, p.stream, D, A, X,
+                       (uint32_t)batch);
     return hipGetLastError();
 }
 // Lockstep width for `level` levels: the LB <= br_pair_lb() with the fewest
@@ -1097,10 +1015,8 @@ template <int LOGN, typename W>
 static hipError_t br_pair_one(const Plan &p, const BrArgs &D, const BrPairX &X, size_t batch, const NttArgs<W> &A,
                               bool coop, int members) {
     switch (members) {
-    case 4: return br_multi_one<LOGN, W, 4, false>(p, D, X, batch, A);
-    case 6: return br_multi_one<LOGN, W, 6, false>(p, D, X, batch, A);
-    case 4 | kBrMultiDense: return br_multi_one<LOGN, W, 4, true>(p, D, X, batch, A);
-    case 6 | kBrMultiDense: return br_multi_one<LOGN, W, 6, true>(p, D, X, batch, A);
+    case 4: return br_multi_one<LOGN, W, 4>(p, D, X, batch, A);
+    case 6: return br_multi_one<LOGN, W, 6>(p, D, X, batch, A);
     default: break;
     }
     constexpr int LM = br_pair_lb<LOGN, W>();
@@ -1143,7 +1059,7 @@ hipError_t launch_br_pair(const Plan &p, int level, int base_log, uint64_t *acc,
                           const uint64_t *lwe_a, const uint64_t *lwe_b, uint32_t lwe_dim, uint64_t lwe_q, size_t batch,
                           void *scratch, const BrPairOpts &o) {
     if (!br_pair_supported(p, 2, batch)) return hipErrorInvalidValue;
-    const int members = o.multi ? br_multi_members(p, level, batch) : 0, nm = members ? members & 0xff : 2;
+    const int members = o.multi ? br_multi_members(p, level, batch) : 0, nm = members ? members : 2;
     const size_t n = (size_t)1 << p.logn, fbytes = br_pair_flag_bytes(batch, nm), abytes = batch * 2 * n * 8;
     uint32_t *flag = (uint32_t *)scratch, *failw = flag + batch * nm;
     uint64_t *acc_in = (uint64_t *)((char *)scratch + fbytes);

@@ -121,11 +121,7 @@ struct Geo {
         const int by_thr = 2048 / THREADS;
         const int wg = by_lds < by_thr ? by_lds : by_thr;
         const int w = wg * THREADS / 64 / 4;
-#ifdef FHE_NO_OCC_BOUND
-        return 1;
-#else
         return w < 1 ? 1 : (w > 8 ? 8 : w);
-#endif
     }
     static constexpr int R(int p) { return (L - p * LOGE) < LOGE ? (L - p * LOGE) : LOGE; }
 };
@@ -214,29 +210,12 @@ __device__ __forceinline__ void lds_load(const W *lds, W (&v)[Geo<LOGN>::E], uin
         for (int t = 0; t < (1 << R); ++t) v[t + (u << R)] = lds[base + pad_idx<LOGN>(uint32_t(t) << S)];
     }
 }
-// Lab-only timing bound (FHE_LAB_NOBAR=1, never in a shipped build: the
-// results are WRONG): the exchanges between passes >= 1 run without their
-// workgroup barriers, i.e. as if each were confined to one wave (a layout
-// whose wave bits avoid the pass digits of both passes).  Measures what
-// barrier-free exchanges could buy before any layout is redesigned.
-#ifndef FHE_LAB_NOBAR
-#define FHE_LAB_NOBAR 0
-#endif
-template <bool LOCAL>
-__device__ __forceinline__ void xbar() {
-    if constexpr (LOCAL) asm volatile("" ::: "memory");
-    else __syncthreads();
-}
-template <int PA, int PB>
-constexpr bool lab_local() { return FHE_LAB_NOBAR && PA >= 1 && PB >= 1; }
-
 // One pass exchange: registers in layout PA -> LDS -> registers in layout PB.
 // The caller's next exchange stores to the positions this one loaded from
 // (same thread, same layout), so no barrier is needed after the load.
 template <int LOGN, int PA, int PB, typename W>
 __device__ __forceinline__ void exchange(W *lds, W (&v)[Geo<LOGN>::E], uint32_t tau) {
     constexpr int E = Geo<LOGN>::E;
-    constexpr bool LOC = lab_local<PA, PB>();
     if constexpr (split_x<LOGN, W>()) {
         uint32_t *l32 = reinterpret_cast<uint32_t *>(lds);
         uint32_t h[E];
@@ -245,18 +224,18 @@ __device__ __forceinline__ void exchange(W *lds, W (&v)[Geo<LOGN>::E], uint32_t 
         lds_store<LOGN, PA>(l32, h, tau);
 #pragma unroll
         for (int e = 0; e < E; ++e) h[e] = (uint32_t)(v[e] >> 32);
-        xbar<LOC>();
+        __syncthreads();
         uint32_t lo[E];
         lds_load<LOGN, PB>(l32, lo, tau);
-        xbar<LOC>();  // every lane's low halves read before the high halves overwrite them
+        __syncthreads();  // every lane's low halves read before the high halves overwrite them
         lds_store<LOGN, PA>(l32, h, tau);
-        xbar<LOC>();
+        __syncthreads();
         lds_load<LOGN, PB>(l32, h, tau);
 #pragma unroll
         for (int e = 0; e < E; ++e) v[e] = (W)lo[e] | ((W)h[e] << 32);
     } else {
         lds_store<LOGN, PA>(lds, v, tau);
-        xbar<LOC>();
+        __syncthreads();
         lds_load<LOGN, PB>(lds, v, tau);
     }
 }
@@ -342,10 +321,7 @@ struct PassTw {
 // on MI355X: 2 for the single-transform kernels (64-VGPR budget at two
 // workgroups per CU), 4 for polymul (one workgroup per CU).
 constexpr int kPfSingle = 2;
-#ifndef FHE_PF_POLYMUL
-#define FHE_PF_POLYMUL 4
-#endif
-constexpr int kPfPolymul = FHE_PF_POLYMUL;
+constexpr int kPfPolymul = 4;
 
 template <int LOGN, int PASS, typename W, int K0 = 0, int K1 = 8>
 __device__ __forceinline__ void load_tw(uint32_t tau, const Tw<W> *__restrict__ tw,
@@ -496,14 +472,11 @@ constexpr bool staged_tw() { return Geo<LOGN>::LOGE >= 5; }
 // butterflies sharing twiddle slot 2^K - 1 + tl), each twiddle loaded SD
 // groups ahead of its single use, so only SD pairs are live.  The first SD
 // loads are issued before the pass's LDS exchange.
-#ifndef FHE_STREAM_TW
-#define FHE_STREAM_TW 1
-#endif
 #ifndef FHE_STREAM_DEPTH
 #define FHE_STREAM_DEPTH 4
 #endif
 template <int LOGN, typename W>
-constexpr bool stream_tw() { return FHE_STREAM_TW && sizeof(W) == 8 && Geo<LOGN>::LOGE == 5; }
+constexpr bool stream_tw() { return sizeof(W) == 8 && Geo<LOGN>::LOGE == 5; }
 // Paired transforms (fwd_poly2 / inv_poly2) at 32 coefficients per thread
 // may stream their twiddles too (two 32-word spectra leave little room for
 // whole-stage twiddle sets).  Per translation unit: measured +1.3 % on the
@@ -514,10 +487,6 @@ constexpr bool stream_tw() { return FHE_STREAM_TW && sizeof(W) == 8 && Geo<LOGN>
 template <int LOGN, typename W>
 constexpr bool stream_tw2() { return FHE_STREAM_TW2 && Geo<LOGN>::LOGE == 5; }
 constexpr int kStreamDepth = FHE_STREAM_DEPTH;
-// 1: a pass's first SD twiddle loads are issued before its LDS exchange
-#ifndef FHE_STREAM_PRE
-#define FHE_STREAM_PRE 1
-#endif
 
 // Stream item i -> (stage k, slot group u, butterfly group tl): forward
 // items run stages 0..R-1, inverse items R-1..0; within a stage, slot group
@@ -642,9 +611,8 @@ __device__ __forceinline__ void fwd_rest(W *lds, W (&v)[Geo<LOGN>::E], uint32_t 
     if constexpr (PASS < G::NP) {
         Tw<W> t[PassTw<LOGN, PASS>::COUNT];
         if constexpr (stream_tw<LOGN, W>()) {
-            if constexpr (FHE_STREAM_PRE) stream_begin<LOGN, PASS, false, false>(tau, tw, t);  // in flight across the exchange
+            stream_begin<LOGN, PASS, false, false>(tau, tw, t);  // in flight across the exchange
             exchange<LOGN, PASS - 1, PASS>(lds, v, tau);
-            if constexpr (!FHE_STREAM_PRE) stream_begin<LOGN, PASS, false, false>(tau, tw, t);
             if constexpr (PASS == G::NP - 1) hook();
             fwd_pass_stream<LOGN, PASS, LAZY, false>(tau, v, t, tw, ar);
             fwd_rest<LOGN, PASS + 1, LAZY, PF>(lds, v, tau, tw, ar, hook);
@@ -693,7 +661,7 @@ __device__ __forceinline__ void fwd_rest2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
         if constexpr (stream_tw2<LOGN, W>()) {
             stream_begin<LOGN, PASS, false, false>(tau, tw, t);
             exchange<LOGN, PASS - 1, PASS>(lds, v, tau);
-            xbar<lab_local<PASS - 1, PASS>()>();
+            __syncthreads();
             exchange<LOGN, PASS - 1, PASS>(lds, v2, tau);
             fwd_pass_stream<LOGN, PASS, LAZY, false, true>(tau, v, t, tw, ar, Scale<W>{}, &v2);
             fwd_rest2<LOGN, PASS + 1, LAZY, PF>(lds, v, v2, tau, tw, ar);
@@ -701,7 +669,7 @@ __device__ __forceinline__ void fwd_rest2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
         }
         load_tw<LOGN, PASS, W, 0, PF>(tau, tw, t);
         exchange<LOGN, PASS - 1, PASS>(lds, v, tau);
-        xbar<lab_local<PASS - 1, PASS>()>();
+        __syncthreads();
         exchange<LOGN, PASS - 1, PASS>(lds, v2, tau);
         fwd_stages2<LOGN, PASS, 0, PF, LAZY>(tau, v, v2, t, tw, ar);
         fwd_rest2<LOGN, PASS + 1, LAZY, PF>(lds, v, v2, tau, tw, ar);
@@ -715,9 +683,8 @@ __device__ __forceinline__ void inv_rest(W *lds, W (&v)[Geo<LOGN>::E], uint32_t 
     if constexpr (PASS >= 0) {
         Tw<W> t[PassTw<LOGN, PASS>::COUNT];
         if constexpr (stream_tw<LOGN, W>()) {
-            if constexpr (FHE_STREAM_PRE) stream_begin<LOGN, PASS, true, FOLD && PASS == 0>(tau, tw, t);
+            stream_begin<LOGN, PASS, true, FOLD && PASS == 0>(tau, tw, t);
             exchange<LOGN, PASS + 1, PASS>(lds, v, tau);
-            if constexpr (!FHE_STREAM_PRE) stream_begin<LOGN, PASS, true, FOLD && PASS == 0>(tau, tw, t);
             inv_pass_stream<LOGN, PASS, FOLD>(tau, v, t, tw, ar, scale);
             inv_rest<LOGN, PASS - 1, FOLD, PF>(lds, v, tau, tw, ar, scale);
             return;
@@ -841,13 +808,10 @@ __device__ __forceinline__ void load_coeffs(W (&v)[E], uint64_t lim, uint64_t q,
     coeffs_from_raw<E>(v, raw, lim, Mod64Red{q, mu});
 }
 
-#ifndef FHE_LOAD_INFLIGHT
-#define FHE_LOAD_INFLIGHT 1
-#endif
+// load chunks in flight ahead of the one being narrowed
+constexpr int kLoadInflight = 1;
 // coefficients per load chunk of the paired transforms (fwd_poly2)
-#ifndef FHE_POLY2_CH
-#define FHE_POLY2_CH 8
-#endif
+constexpr int kPoly2Chunk = 8;
 // As load_coeffs, for 32 coefficients per thread: raw u64 words are 2 VGPRs
 // each, so only IN chunks of CH are in flight at once and each chunk is
 // narrowed before the next is issued (scheduling barriers keep the compiler
@@ -891,15 +855,6 @@ __device__ __forceinline__ void load_coeffs_chunked(W (&v)[E], uint64_t lim, RD 
 // Sub-transform use (N > 16384, ntt_big.hip): the 2^LOGN coefficients are
 // the strided subsequence src[i << sh] of a larger polynomial; the prefix
 // stages of the big transform use the same stage-major twiddles.
-// Raw pass-0 coefficients of a P == 1 polynomial (bit-reversed order), for
-// prefetching through a fwd_rest hook.
-template <int LOGN>
-__device__ __forceinline__ void load_raw(uint64_t (&raw)[Geo<LOGN>::E], uint32_t tau, const uint64_t *src) {
-    using G = Geo<LOGN>;
-    const auto r = brsrc(src);
-#pragma unroll
-    for (int t = 0; t < G::E; ++t) raw[t] = bload(r, tau * 8u, cbrv(t, G::LOGE) * G::T * 8u);
-}
 template <int LOGN, bool LAZY, int PF = kPfSingle, bool RS = false, typename W, typename H = NoHook>
 __device__ __forceinline__ void fwd_poly(W *lds, W (&v)[Geo<LOGN>::E], uint32_t tau, const uint64_t *__restrict__ src,
                                          bool valid, const NttArgs<W> &A, uint32_t sh = 0, H &&hook = NoHook{}, uint64_t (*pre)[Geo<LOGN>::E] = nullptr) {
@@ -910,13 +865,13 @@ __device__ __forceinline__ void fwd_poly(W *lds, W (&v)[Geo<LOGN>::E], uint32_t 
     if constexpr (!ST) load_tw<LOGN, 0>(tau, twf, t0);
     // a Shoup-based first step (R-scaling) accepts any word
     const uint64_t lim = RS ? (uint64_t)(W)~W(0) : (uint64_t)(A.ar.q2 * 2);
-    if (pre) {  // prefetched by the caller (load_raw)
+    if (pre) {  // raw pass-0 words the caller already holds
         coeffs_from_raw<G::E>(v, *pre, lim, SlowRed<W>{A});
     } else if constexpr (G::P == 1) {  // the caller has returned early if !valid
         const auto r = brsrc(src);
         const uint32_t vo = (tau << sh) * 8u;
         auto at = [&](int t) -> uint64_t { return bload(r, vo, ((cbrv(t, G::LOGE) * G::T) << sh) * 8u); };
-        if constexpr (G::LOGE == 5) load_coeffs_chunked<G::E, 8, FHE_LOAD_INFLIGHT>(v, lim, SlowRed<W>{A}, at);
+        if constexpr (G::LOGE == 5) load_coeffs_chunked<G::E, 8, kLoadInflight>(v, lim, SlowRed<W>{A}, at);
         else load_coeffs_r<G::E>(v, lim, SlowRed<W>{A}, at);
     } else {
         load_coeffs_r<G::E>(v, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
@@ -948,13 +903,13 @@ __device__ __forceinline__ void fwd_poly2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
     const uint32_t vo = tau * 8u;
     {
         const auto r = brsrc(src);
-        load_coeffs_chunked<G::E, FHE_POLY2_CH, FHE_LOAD_INFLIGHT>(v, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
+        load_coeffs_chunked<G::E, kPoly2Chunk, kLoadInflight>(v, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
             return bload(r, vo, cbrv(t, G::LOGE) * G::T * 8u);
         });
     }
     {
         const auto r = brsrc(src2);
-        load_coeffs_chunked<G::E, FHE_POLY2_CH, FHE_LOAD_INFLIGHT>(v2, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
+        load_coeffs_chunked<G::E, kPoly2Chunk, kLoadInflight>(v2, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
             return bload(r, vo, cbrv(t, G::LOGE) * G::T * 8u);
         });
     }
@@ -1032,7 +987,7 @@ __device__ __forceinline__ void inv_rest2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
         if constexpr (stream_tw2<LOGN, W>()) {
             stream_begin<LOGN, PASS, true, FOLD && PASS == 0>(tau, tw, t);
             exchange<LOGN, PASS + 1, PASS>(lds, v, tau);
-            xbar<lab_local<PASS + 1, PASS>()>();
+            __syncthreads();
             exchange<LOGN, PASS + 1, PASS>(lds, v2, tau);
             inv_pass_stream<LOGN, PASS, FOLD, true>(tau, v, t, tw, ar, scale, &v2);
             inv_rest2<LOGN, PASS - 1, FOLD, PF>(lds, v, v2, tau, tw, ar, scale);
@@ -1042,7 +997,7 @@ __device__ __forceinline__ void inv_rest2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
         constexpr int KS = R - PF < 0 ? 0 : R - PF;
         load_tw<LOGN, PASS, W, KS, 8>(tau, tw, t);
         exchange<LOGN, PASS + 1, PASS>(lds, v, tau);
-        xbar<lab_local<PASS + 1, PASS>()>();
+        __syncthreads();
         exchange<LOGN, PASS + 1, PASS>(lds, v2, tau);
         inv_stages2<LOGN, PASS, R - 1, R - KS, FOLD>(tau, v, v2, t, tw, ar, scale);
         inv_rest2<LOGN, PASS - 1, FOLD, PF>(lds, v, v2, tau, tw, ar, scale);

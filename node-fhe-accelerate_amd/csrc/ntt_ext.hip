@@ -54,10 +54,7 @@ namespace FHE_NS {
 // waves per CU resident: at N = 1024 with u64 words they would cut the CU to
 // one 4-wave workgroup (99 KB of LDS), and the HBM/L2 round trip of the
 // output-row stash is cheaper than that loss of latency hiding.
-#ifndef FHE_EXT_MINWAVES
-#define FHE_EXT_MINWAVES 8
-#endif
-constexpr int kExtMinWaves = FHE_EXT_MINWAVES;
+constexpr int kExtMinWaves = 8;
 template <int LOGN, typename W, int K1, int MODE = 0>
 constexpr int ext_stash() {
     using G = Geo<LOGN>;
@@ -69,10 +66,7 @@ constexpr int ext_stash() {
     // relinearisation (MODE 1): accumulator 0 in LDS, accumulator 1 and the
     // c2 words in VGPRs (one workgroup per CU); c2 is then read once instead
     // of once per digit level
-#ifndef FHE_RELIN_REGS
-#define FHE_RELIN_REGS 1
-#endif
-    if (FHE_RELIN_REGS && MODE == 1 && K1 == 2 && G::P == 1 && (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024)
+    if (MODE == 1 && K1 == 2 && G::P == 1 && (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024)
         return 3;
     return 2;
 }
@@ -105,15 +99,12 @@ struct DmArgs {
 // transform in one batch instead of two coefficients at a time: 8.14 vs 8.30 ms
 // per 16,384 ciphertexts (round 5).  Issued before the transform (kept in
 // flight across it) it spills 28 VGPRs and takes 10.4 ms.
-#ifndef FHE_RELIN_KPF
-#define FHE_RELIN_KPF 1
-#endif
 template <int LOGN, typename W, int K1, bool LAZY, int MODE>
 __global__ void __launch_bounds__(Geo<LOGN>::THREADS, (ext_occ<LOGN, W, K1, MODE>()))
 k_dmac(DmArgs D, NttArgs<W> A) {
     using G = Geo<LOGN>;
     constexpr int STASH = ext_stash<LOGN, W, K1, MODE>();
-    constexpr int KPF = (MODE == 1 && STASH == 3 && sizeof(W) == 4) ? FHE_RELIN_KPF : 0;
+    constexpr bool KPF = MODE == 1 && STASH == 3 && sizeof(W) == 4;
     constexpr int NIN = MODE == 1 ? 3 : K1;  // source polynomials per ciphertext
     __shared__ W lds_all[G::P * G::LW + ext_extra_words<LOGN, W, K1, MODE>()];
     const uint32_t tau = threadIdx.x & (G::T - 1), pl = wg_poly<G>();
@@ -180,8 +171,7 @@ k_dmac(DmArgs D, NttArgs<W> A) {
             }
             return d;
         });
-        // KPF: the row's key words loaded at once, before (2) or after (1)
-        // the digit transform
+        // KPF: the row's key words loaded at once, after the digit transform
         uint32_t kw[KPF ? G::E : 1][2];
         auto load_keys = [&]() {
             const uint32_t *g32 = reinterpret_cast<const uint32_t *>(D.key + (size_t)r * K1 * G::N);
@@ -191,12 +181,11 @@ k_dmac(DmArgs D, NttArgs<W> A) {
                 for (int j = 0; j < 2; ++j)
                     kw[e][j] = g32[2 * ((size_t)(1 - j) * G::N + gidx<LOGN, G::NP - 1>(tr, e))];
         };
-        if constexpr (KPF == 2) load_keys();
         fwd_pass<LOGN, 0, LAZY>(v, t0, A.ar);
         fwd_rest<LOGN, 1, LAZY, kPfSingle>(lds, v, tr, A.twf, A.ar);
-        if constexpr (KPF == 1) load_keys();
+        if constexpr (KPF) load_keys();
         if (!valid) continue;
-        if constexpr (KPF != 0) {
+        if constexpr (KPF) {
 #pragma unroll
             for (int e = 0; e < G::E; ++e) {
                 const uint32_t gi = gidx<LOGN, G::NP - 1>(tr, e);
@@ -273,164 +262,18 @@ k_dmac(DmArgs D, NttArgs<W> A) {
     }
 }
 
-// Relinearisation at two workgroups per CU (lab build
-// FHE_RELIN2=1, measured SLOWER and not dispatched: per 16,384 ciphertexts
-// 9.11 ms with accumulator 1 in VGPRs (6 VGPRs spilled, FHE_RELIN2_ACC1G=0)
-// and 10.11 ms with both accumulators in the output rows (spill-free), against
-// 8.19 ms for k_dmac MODE 1; parity green, profiles/r6d).  k_dmac
-// MODE 1 keeps accumulator 0 in LDS beside the 64 KiB exchange (133 KB: one
-// 16-wave workgroup per CU).  Here one 512-thread workgroup per ciphertext
-// holds 32 coefficients per thread; accumulator 1 stays in VGPRs and
-// accumulator 0 lives in the ciphertext's own output row 0, used as [N] u32
-// scratch (read-modify-write of the thread's own positions, L2-resident, no
-// synchronisation) until that row's final stores -- so the LDS is the
-// exchange alone (64 KiB) and two workgroups share a CU.  c2 is re-read per
-// digit level (L2 / MALL) instead of held in VGPRs.  Same digit map,
-// Montgomery MAC, red2q accumulation and N^-1 inverse + c_j epilogue as
-// k_dmac MODE 1: bit-identical outputs.
-#ifndef FHE_RELIN2
-#define FHE_RELIN2 0
-#endif
-#ifndef FHE_RELIN2_MC
-#define FHE_RELIN2_MC 2
-#endif
-#ifndef FHE_RELIN2_PF
-#define FHE_RELIN2_PF 1
-#endif
-#ifndef FHE_RELIN2_ACC1G
-#define FHE_RELIN2_ACC1G 0
-#endif
-constexpr int kRelin2Key = gk(14, 5);
-__device__ __forceinline__ uint32_t bload32(__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0);
-}
-__device__ __forceinline__ void bstore32(__amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so, uint32_t x) {
-    __builtin_amdgcn_raw_buffer_store_b32(x, r, vo, so, 0);
-}
-template <int K>
-__global__ void __launch_bounds__(Geo<K>::THREADS, Geo<K>::template occ_waves<uint32_t>())
-k_relin2(DmArgs D, NttArgs<uint32_t> A) {
-    using G = Geo<K>;
-    using W = uint32_t;
-    static_assert(G::P == 1 && G::E == 32, "one ciphertext per workgroup, 32 coefficients per thread");
-    constexpr int N = G::N, E = G::E, MC = FHE_RELIN2_MC, NC = E / MC;
-    __shared__ W lds[lds_elems<K, W>()];
-    const TidSource lane;
-    const size_t ct = blockIdx.x;
-    if (ct >= D.batch) return;  // whole workgroup
-    const uint64_t *srow = D.src + ct * 3 * N;
-    uint64_t *orow = D.out + ct * 2 * N;
-    const auto racc0 = brsrc(orow);  // accumulator 0: row 0 as u32 words at 4 gi
-    const auto racc1 = brsrc(orow + N);  // FHE_RELIN2_ACC1G: accumulator 1 likewise in row 1
-    const int level = D.level;
-    const uint64_t mask = (1ull << D.base_log) - 1;
-    const uint64_t q = A.q64, mu = A.mu64, lim = (uint64_t)A.ar.q2 * 2;
-    W racc[FHE_RELIN2_ACC1G ? 1 : E];
-    for (int l = 0; l < level; ++l) {
-        const uint32_t tr = lane();
-        const uint32_t shift = uint32_t(l) * uint32_t(D.base_log);
-        W v[E];
-        {
-            const auto rs = brsrc(srow + 2 * N);
-            // (SlowRed: the 32-bit-friendly exact reduction of out-of-range
-            // digits; mod64_slow's 64-bit Barrett step spills here)
-            load_coeffs_chunked<E, 8, 1>(v, lim, SlowRed<W>{A}, [&](int t) -> uint64_t {
-                return (bload(rs, tr * 8u, cbrv(t, G::LOGE) * G::T * 8u) >> shift) & mask;
-            });
-        }
-        if (l > 0) __syncthreads();  // the previous transform's last exchange reads precede these stores
-        {
-            Tw<W> t0[PassTw<K, 0>::COUNT];
-            load_tw<K, 0>(tr, A.twf, t0);
-            fwd_pass<K, 0, false>(v, t0, A.ar);
-        }
-        fwd_rest<K, 1, false, FHE_RELIN2_PF>(lds, v, tr, A.twf, A.ar);
-        // key low words (canonical prepared residues < q < 2^32): c0' takes
-        // b_l (row 1), c1' a_l (row 0); chunk c + 1 in flight while chunk c
-        // is consumed
-        const auto rb = brsrc(D.key + ((size_t)l * 2 + 1) * N), ra = brsrc(D.key + (size_t)l * 2 * N);
-        const uint32_t vo = LastIO<K>::vo(lane());
-        // one chunk in flight (nk*) while the previous one (ck*) is consumed
-        uint32_t nkb[MC], nka[MC], na0[MC], na1[MC];
-        auto issue = [&](int c) {
-#pragma unroll
-            for (int i = 0; i < MC; ++i) {
-                const uint32_t so = LastIO<K>::so(c * MC + i);
-                nkb[i] = bload32(rb, vo, so);
-                nka[i] = bload32(ra, vo, so);
-                if (l > 0) na0[i] = bload32(racc0, vo / 2u, so / 2u);
-                if (FHE_RELIN2_ACC1G && l > 0) na1[i] = bload32(racc1, vo / 2u, so / 2u);
-            }
-        };
-        issue(0);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            uint32_t ckb[MC], cka[MC], ca0[MC], ca1[MC];
-#pragma unroll
-            for (int i = 0; i < MC; ++i) ckb[i] = nkb[i], cka[i] = nka[i], ca0[i] = na0[i], ca1[i] = na1[i];
-            if (c + 1 < NC) issue(c + 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MC; ++i) {
-                const int e = c * MC + i;
-                const uint32_t so = LastIO<K>::so(e);
-                // raw output (< 4q) times a canonical key: valid Montgomery pair
-                const W m0 = A.ar.mont(v[e], ckb[i]), m1 = A.ar.mont(v[e], cka[i]);
-                bstore32(racc0, vo / 2u, so / 2u, A.ar.red2q((l > 0 ? ca0[i] : W(0)) + m0));
-                if constexpr (FHE_RELIN2_ACC1G)
-                    bstore32(racc1, vo / 2u, so / 2u, A.ar.red2q((l > 0 ? ca1[i] : W(0)) + m1));
-                else
-                    racc[FHE_RELIN2_ACC1G ? 0 : e] = A.ar.red2q((l > 0 ? racc[FHE_RELIN2_ACC1G ? 0 : e] : W(0)) + m1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // c_j' = inv(acc_j) + c_j (encryption.cpp:953/958), row 0 first: its
-    // scratch words are read into registers before the inverse's first
-    // exchange barrier, its final stores come after the last one
-    auto fin = [&](int j) {
-        return [&, j](uint32_t gi, uint64_t x) -> uint64_t { return addq(x, red_q(srow[(size_t)j * N + gi], q, mu), q); };
-    };
-    __syncthreads();
-    {
-        const uint32_t ti = lane();
-        const uint32_t vo = LastIO<K>::vo(ti);
-        W v[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) v[e] = bload32(racc0, vo / 2u, LastIO<K>::so(e) / 2u);
-        inv_poly_from_regs<K, FHE_RELIN2_PF>(lds, v, ti, orow, true, A, A.ninv, 0, fin(0));
-    }
-    __syncthreads();
-    const uint32_t ti = lane();
-    if constexpr (FHE_RELIN2_ACC1G) {
-        const uint32_t vo = LastIO<K>::vo(ti);
-        W v[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) v[e] = bload32(racc1, vo / 2u, LastIO<K>::so(e) / 2u);
-        inv_poly_from_regs<K, FHE_RELIN2_PF>(lds, v, ti, orow + N, true, A, A.ninv, 0, fin(1));
-    } else {
-        inv_poly_from_regs<K, FHE_RELIN2_PF>(lds, racc, ti, orow + N, true, A, A.ninv, 0, fin(1));
-    }
-}
-
 // External product with one decomposition level (level == 1, K1 == 2) for
 // one polynomial per workgroup: the two digit polynomials are transformed in
 // lockstep (shared twiddles), the key MAC turns (X0, X1) into the two
 // NTT-domain outputs in place, and both inverses run in lockstep -- nothing
 // is parked in HBM (k_dmac's output-row stash read and wrote every
 // accumulator once per row: 2.2x the algorithmic traffic at N = 16384).
-#ifndef FHE_EXT2_PF
-#define FHE_EXT2_PF 0
-#endif
-#ifndef FHE_EXT2
-#define FHE_EXT2 1
-#endif
 template <int LOGN, typename W>
 __global__ void __launch_bounds__(Geo<LOGN>::THREADS, Geo<LOGN>::template occ_waves<W>())
 k_extprod2(DmArgs D, NttArgs<W> A) {
     using G = Geo<LOGN>;
     static_assert(G::P == 1, "one ciphertext per workgroup");
-    constexpr int PF = FHE_EXT2_PF;
+    constexpr int PF = 0;  // no twiddle stage ahead of the exchanges: two 16-word spectra are live
     __shared__ W lds[G::LW];
     const TidSource tid;  // lane index per phase, not held across phases
     const uint32_t tau = tid();
@@ -482,19 +325,16 @@ k_extprod2(DmArgs D, NttArgs<W> A) {
 // waves per CU) measured slower on MI355X: single digit transforms 9.03 vs
 // 8.29 ms per 16,384 ciphertexts (round 4), digit levels in lockstep pairs
 // 4.67 vs 4.27 ms per 8,192 (round 5) -- the 16 waves of MODE 1 hide more of
-// the exchange barriers than the shorter transforms save.
+// the exchange barriers than the shorter transforms save.  One 512-thread
+// workgroup per ciphertext with accumulator 0 in the output row (two
+// workgroups per CU) measured 9.11 ms against 8.19 ms (profiles/r6d).
 
-// FHE_EXT_ACC=0: multi-level external products at N = 16384 take k_dmac
-// (lab A/B against ntt_ext2.hip).
-#ifndef FHE_EXT_ACC
-#define FHE_EXT_ACC 1
-#endif
 template <int LOGN, typename W, int MODE>
 static hipError_t dmac_one(const NttArgs<W> &A, hipStream_t s, int k1, const DmArgs &D) {
     using G = Geo<LOGN>;
     const size_t blocks = (D.batch + G::P - 1) / G::P;
     if (k1 != 2) return hipErrorInvalidValue;
-    if constexpr (MODE == 0 && G::P == 1 && FHE_EXT2 && sizeof(W) == 8 && LOGN >= 12) {
+    if constexpr (MODE == 0 && G::P == 1 && sizeof(W) == 8 && LOGN >= 12) {
         if (D.level == 1) {
             if constexpr (LOGN == 14) {
                 // a sparse prime (ntt_core.hpp gk_sparse): C5 (23, 1) 8.1 -> 7.7 ms
@@ -512,10 +352,6 @@ static hipError_t dmac_one(const NttArgs<W> &A, hipStream_t s, int k1, const DmA
             hipLaunchKernelGGL((k_extprod2<LOGN, W>), dim3((unsigned)D.batch), dim3(G::THREADS), 0, s, D, A);
             return hipGetLastError();
         }
-    }
-    if constexpr (FHE_RELIN2 && MODE == 1 && LOGN == 14 && sizeof(W) == 4) {
-        hipLaunchKernelGGL((k_relin2<kRelin2Key>), dim3((unsigned)D.batch), dim3(Geo<kRelin2Key>::THREADS), 0, s, D, A);
-        return hipGetLastError();
     }
     // (unit twiddles, ntt_core.hpp gk_compat, measured 0 to +0.4 % here and in
     // the external-product kernels, round 5: not instantiated)
@@ -545,7 +381,7 @@ static hipError_t dmac(const Plan &p, int k1, const DmArgs &D) {
 
 hipError_t launch_extprod(const Plan &p, int k1, int level, int base_log, const uint64_t *glwe,
                           const uint64_t *ggsw, uint64_t *out, size_t batch) {
-    if (FHE_EXT_ACC && extprod_acc_supported(p, k1, level, base_log))
+    if (extprod_acc_supported(p, k1, level, base_log))
         return launch_extprod_acc(p, level, base_log, glwe, ggsw, out, batch);
     DmArgs D{glwe, ggsw, out, batch, level, base_log, nullptr, 0, 0, 0, nullptr};
     return dmac<0>(p, k1, D);

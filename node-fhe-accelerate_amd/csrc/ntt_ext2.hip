@@ -38,27 +38,15 @@
 #endif
 #include "fhe_internal.hpp"
 #include "lwe_ops.hpp"
-#ifndef FHE_EXTACC_MC
-#define FHE_EXTACC_MC 4
-#endif
-// key chunks in flight ahead of their use; issue the first ones in the last pass
-#ifndef FHE_EXTACC_PD
-#define FHE_EXTACC_PD 1
-#endif
-#ifndef FHE_EXTACC_HOOK
-#define FHE_EXTACC_HOOK 0
-#endif
-// lab: the 62-bit sparse prime compiled in (ntt_core.hpp gk_sparse), as in
-// k_extprod2 for (23, 1): 0.4 % fewer static issue
-// cycles, spill-free, but 13.33 vs 13.05 ms per 16,384 at (15, 2) (round 6,
-// profiles/r6h): not dispatched
-#ifndef FHE_EXTACC_SPARSE
-#define FHE_EXTACC_SPARSE 0
-#endif
 
 namespace FHE_NS {
 
 constexpr int kExtAccKey = gk(14, 5);
+// key words per chunk, and chunks in flight ahead of their use.  (The 62-bit
+// sparse prime compiled in, as in k_extprod2: 0.4 % fewer static issue cycles,
+// spill-free, but 13.33 vs 13.05 ms per 16,384 at (15, 2), profiles/r6h.)
+constexpr int kExtAccChunk = 4;
+constexpr int kExtAccAhead = 1;
 
 struct ExtAccArgs {
     const uint64_t *glwe;  // [batch][2][N]
@@ -72,7 +60,7 @@ __global__ void __launch_bounds__(Geo<K>::THREADS, 2) k_extprod_acc(ExtAccArgs D
     using G = Geo<K>;
     using W = uint64_t;
     static_assert(G::P == 1 && G::E == 32, "one ciphertext per workgroup, 32 coefficients per thread");
-    constexpr int N = G::N, E = G::E, MC = FHE_EXTACC_MC;
+    constexpr int N = G::N, E = G::E, MC = kExtAccChunk;
     __shared__ W lds[lds_elems<K, W>()];
     __shared__ int32_t plane[N];  // level-1 digits of the current row (signed)
     // the lane index is rebuilt per row (TidSource): a VGPR holding it across
@@ -123,11 +111,11 @@ __global__ void __launch_bounds__(Geo<K>::THREADS, 2) k_extprod_acc(ExtAccArgs D
             fwd_pass_stream<K, 0, false, false>(tr, v, t0, A.twf, A.ar);
         }
         // The row's key words stream in chunks of MC coefficients: the first
-        // PD chunks are issued inside the transform's last pass (hook), then
-        // chunk c + PD before chunk c is consumed -- the L2 round trips
-        // overlap instead of following each other (they did, one per chunk).
+        // PD chunks are issued after the transform, then chunk c + PD before
+        // chunk c is consumed -- the L2 round trips overlap instead of
+        // following each other (they did, one per chunk).
         const auto rk = brsrc(D.key + (size_t)r * 2 * N);
-        constexpr int NC = E / MC, PD = FHE_EXTACC_PD;
+        constexpr int NC = E / MC, PD = kExtAccAhead;
         uint64_t k0[E], k1[E];
         auto issue = [&](int c) {
             const uint32_t vo = LastIO<K>::vo(lane_index());
@@ -137,13 +125,9 @@ __global__ void __launch_bounds__(Geo<K>::THREADS, 2) k_extprod_acc(ExtAccArgs D
                 k1[e] = bload<0>(rk, vo, LastIO<K>::so(e) + N * 8u);
             }
         };
-        auto hook = [&] {
+        fwd_rest<K, 1, false, kPfSingle>(lds, v, tr, A.twf, A.ar);
 #pragma unroll
-            for (int c = 0; c < (FHE_EXTACC_HOOK ? PD : 0) && c < NC; ++c) issue(c);
-        };
-        fwd_rest<K, 1, false, kPfSingle>(lds, v, tr, A.twf, A.ar, hook);
-#pragma unroll
-        for (int c = FHE_EXTACC_HOOK ? PD : 0; c < PD && c < NC; ++c) issue(c);
+        for (int c = 0; c < PD && c < NC; ++c) issue(c);
         // raw outputs (< 4q) times canonical prepared keys: valid Montgomery pairs
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -175,12 +159,8 @@ hipError_t launch_extprod_acc(const Plan &p, int level, int base_log, const uint
     for (size_t b0 = 0; b0 < batch; b0 += per) {
         const size_t nb = batch - b0 < per ? batch - b0 : per;
         ExtAccArgs D{glwe + b0 * 2 * ((size_t)1 << 14), ggsw, out + b0 * 2 * ((size_t)1 << 14), level, base_log};
-        if (FHE_EXTACC_SPARSE && p.a64.ar.sp == 1)
-            hipLaunchKernelGGL((k_extprod_acc<gk_sparse(kExtAccKey, 1)>), dim3((unsigned)nb),
-                               dim3(Geo<kExtAccKey>::THREADS), 0, p.stream, D, p.a64);
-        else
-            hipLaunchKernelGGL((k_extprod_acc<kExtAccKey>), dim3((unsigned)nb), dim3(Geo<kExtAccKey>::THREADS), 0,
-                               p.stream, D, p.a64);
+        hipLaunchKernelGGL((k_extprod_acc<kExtAccKey>), dim3((unsigned)nb), dim3(Geo<kExtAccKey>::THREADS), 0,
+                           p.stream, D, p.a64);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

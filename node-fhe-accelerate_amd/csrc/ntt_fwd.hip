@@ -64,21 +64,11 @@ k_ntt_fwd_limbs(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, siz
     ntt_fwd_body<LOGN, W, LAZY, 0>(in + o, out + o, batch, A);
 }
 
-#ifndef FHE_FWDMUL_PREFETCH
-#define FHE_FWDMUL_PREFETCH 1
-#endif
-// 32 words per thread: w in chunks of FHE_FWDMUL_CH words, FHE_FWDMUL_PD
-// chunks in flight ahead of their use, the first FHE_FWDMUL_HOOK of them
-// issued inside the transform's last pass
-#ifndef FHE_FWDMUL_CH
-#define FHE_FWDMUL_CH 4
-#endif
-#ifndef FHE_FWDMUL_PD
-#define FHE_FWDMUL_PD 1
-#endif
-#ifndef FHE_FWDMUL_HOOK
-#define FHE_FWDMUL_HOOK 1
-#endif
+// 32 words per thread: w in chunks of kFwdMulChunk words, kFwdMulAhead
+// chunks in flight ahead of their use, issued first inside the transform's
+// last pass
+constexpr int kFwdMulChunk = 4;
+constexpr int kFwdMulAhead = 1;
 template <int LOGN, typename W, bool LAZY>
 __global__ void __launch_bounds__(Geo<LOGN>::THREADS, Geo<LOGN>::template occ_waves<W>())
 k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, uint64_t *__restrict__ out,
@@ -96,7 +86,6 @@ k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, 
     // Montgomery pair.
     const uint64_t *wp = wv + poly * G::N;
     uint64_t *dst = out + poly * G::N;
-#if FHE_FWDMUL_PREFETCH
     if constexpr (G::P == 1 && G::E <= 16) {  // 32 raw u64 words would not fit beside the spectrum
         // w is loaded during the last pass (its HBM latency overlaps it)
         uint64_t rw[G::E];
@@ -114,15 +103,13 @@ k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, 
         for (int e = 0; e < G::E; ++e) bstore(ro, vo, LastIO<LOGN>::so(e), (uint64_t)A.ar.red1q(A.ar.mont(v[e], w[e])));
         return;
     }
-#endif
-#if FHE_FWDMUL_PREFETCH
     if constexpr (G::P == 1 && G::E == 32) {
-        // 32 words per thread (64-bit lanes): w streams in chunks of 8 --
-        // the first FHE_FWDMUL_PD chunks are issued in the last pass (hook),
-        // then chunk c + IN is issued before chunk c is consumed, so the
+        // 32 words per thread (64-bit lanes): w streams in chunks -- the
+        // first kFwdMulAhead chunks are issued in the last pass (hook), then
+        // chunk c + kFwdMulAhead is issued before chunk c is consumed, so the
         // loads of w overlap the transform's tail and each other instead of
         // one round trip per chunk after the transform.
-        constexpr int CH = FHE_FWDMUL_CH, NC = G::E / CH;
+        constexpr int CH = kFwdMulChunk, PD = kFwdMulAhead, NC = G::E / CH;
         uint64_t rw[G::E];
         const uint32_t vo = LastIO<LOGN>::vo(tau);
         const auto rwr = brsrc(wp);
@@ -132,15 +119,13 @@ k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, 
         };
         auto hook = [&] {
 #pragma unroll
-            for (int c = 0; c < FHE_FWDMUL_HOOK && c < NC; ++c) issue(c);
+            for (int c = 0; c < PD && c < NC; ++c) issue(c);
         };
         fwd_poly<LOGN, LAZY, kPfSingle, true>(lds, v, tau, in + poly * G::N, valid, A, 0, hook);
         const auto ro = brsrc(dst);
 #pragma unroll
-        for (int c = FHE_FWDMUL_HOOK; c < FHE_FWDMUL_PD && c < NC; ++c) issue(c);
-#pragma unroll
         for (int c = 0; c < NC; ++c) {
-            if (c + FHE_FWDMUL_PD < NC) issue(c + FHE_FWDMUL_PD);
+            if (c + PD < NC) issue(c + PD);
             __builtin_amdgcn_sched_barrier(0);
             W w[CH];
             uint64_t r8[CH];
@@ -154,7 +139,6 @@ k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, 
         }
         return;
     }
-#endif
     fwd_poly<LOGN, LAZY, kPfSingle, true>(lds, v, tau, in + poly * G::N, valid, A);
     if (!valid) return;
     // two chunks: 16 raw u64 w in flight at once would exceed 64 VGPRs
@@ -186,11 +170,8 @@ k_ntt_fwd_mul(const uint64_t *__restrict__ in, const uint64_t *__restrict__ wv, 
 // 64-bit words at N = 16384: 32 coefficients per thread (512 threads,
 // radix-32 passes: 2 exchanges instead of 3) and the split exchange, so two
 // workgroups share a CU at <= 128 VGPRs each.
-#ifndef FHE_FWD64_E32
-#define FHE_FWD64_E32 1
-#endif
 template <int LOGN, typename W>
-constexpr int fwd_key() { return (FHE_FWD64_E32 && sizeof(W) == 8 && LOGN == 14) ? gk(LOGN, 5) : LOGN; }
+constexpr int fwd_key() { return (sizeof(W) == 8 && LOGN == 14) ? gk(LOGN, 5) : LOGN; }
 
 template <int LOGN0, typename W, bool LAZY>
 static hipError_t fwd_one(const NttArgs<W> &A, hipStream_t s, const uint64_t *in, uint64_t *out, size_t batch,

@@ -65,111 +65,53 @@ k_ntt_inv_limbs(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, siz
     ntt_inv_body<LOGN, W>(in + o, out + o, batch, A);
 }
 
-// Where fwd(a) waits while fwd(b) runs: 0 = VGPRs (small N), 1 = a second
-// LDS region, 2 = the output row in HBM (u64 at N = 16384, where LDS is
-// full and the kernel is ALU-bound, so 16N extra bytes are cheap).  Keeping
-// both spectra in VGPRs cost 150-255 VGPRs (N <= 8192) or scratch spills
-// (N = 16384).
-#ifndef FHE_POLY_PREFETCH
-#define FHE_POLY_PREFETCH 1
-#endif
-#ifndef FHE_POLY_HBM_STASH
-#define FHE_POLY_HBM_STASH 0
-#endif
-#ifndef FHE_POLY_REG_STASH_14
-#define FHE_POLY_REG_STASH_14 0
-#endif
+// Which polymul kernel runs (degree, word size):
+//   k_polymul2 (fwd(a) and fwd(b) in lockstep, no stash of fwd(a)):
+//     32-bit words at N = 8192 / 16384 with 32 coefficients per thread
+//     (radix-32 passes: 2 LDS exchanges per transform instead of 3, N/32
+//     threads, conflict-free pads, two workgroups per CU so one's HBM traffic
+//     overlaps the other's transforms), and at N = 4096 with 16 per thread
+//     (one 256-thread workgroup per pair, <= 128 VGPRs): 30.3 -> 28.1 us for
+//     C2's 1024 pairs, 1.67 -> 1.49 ms (q < 2^27, lazy) and 1.74 -> 1.62 ms
+//     (q < 2^30) per 65,536 (round 5);
+//     64-bit words at N = 4096 .. 16384 with 16 per thread (two 16-word u64
+//     spectra = 64 VGPRs; occupancy floor 4 waves per SIMD below N = 16384;
+//     123-126 VGPRs, no spill): per 16,384 pairs at N = 8192 2.83 -> 2.23 ms
+//     (Q_60_1) and 2.75 -> 2.10 ms (the 62-bit prime), at N = 4096 1.23 ->
+//     1.06 ms (Q_60_1) (round 5).  32 per thread with streamed twiddles and
+//     fwd(a) stashed in c's row measured slower at N = 16384.
+//   k_polymul (one transform at a time, fwd(a) parked meanwhile): every
+//     smaller degree.
 template <int LOGN, typename W>
-constexpr int polymul_stash() {
-    using G = Geo<LOGN>;
-    if (G::LOGE == 5 && sizeof(W) == 8) return 2;  // 64-bit words: two 64-word spectra do not fit
-    if (G::L < 5 || G::LOGE == 5) return 0;  // 32 coefficients per thread: fwd(a) stays in VGPRs
-    if (FHE_POLY_REG_STASH_14 && G::L == 14 && sizeof(W) == 4) return 0;
-    if (FHE_POLY_HBM_STASH && G::L == 14) return 2;
-    return G::P * (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024 ? 1 : 2;
-}
+constexpr int polymul_key() { return (sizeof(W) == 4 && LOGN >= 13 && LOGN <= 14) ? gk(LOGN, 5) : LOGN; }
 template <int LOGN, typename W>
-constexpr int polymul_occ() {
-    // with the stash in HBM the LDS footprint admits a second workgroup
-    if (polymul_stash<LOGN, W>() == 0 && Geo<LOGN>::L >= 12) return Geo<LOGN>::template occ_waves<W>();
-    return polymul_stash<LOGN, W>() == 2 && (FHE_POLY_HBM_STASH || Geo<LOGN>::LOGE == 5)
-               ? Geo<LOGN>::template occ_waves<W>() : 1;
-}
-// Polymul geometry: at q < 2^30 and N >= 4096, 32 coefficients per thread
-// (radix-32 passes: 2 LDS exchanges per transform instead of 3, N/32 threads,
-// fwd(a) parked in VGPRs, conflict-free pads, two workgroups per CU so one's
-// HBM traffic overlaps the other's transforms).  FHE_POLY_E16=1: the 16-per-
-// thread kernel with the LDS stash (lab A/B).
-#ifndef FHE_POLY_E16
-#define FHE_POLY_E16 0
-#endif
-#ifndef FHE_PF_POLY32
-#define FHE_PF_POLY32 1
-#endif
-// 64-bit words at N = 16384 (FHE_POLY64): 1 = the dual kernel at 16
-// coefficients per thread (one workgroup per CU, 128 VGPRs, no stash);
-// 2 = 32 per thread with streamed twiddles, the split exchange and fwd(a)
-// stashed in c's row (two workgroups per CU, 1.67x the algorithmic bytes).
-#ifndef FHE_POLY64
-#define FHE_POLY64 1
-#endif
-// Inverse transform key: FHE_INV64_E32=1 runs 64-bit words at N = 16384 at
-// 32 coefficients per thread with streamed twiddles and the split exchange
-// (as the forward).  Measured slower than 16 per thread (7.91 vs 7.62 ms per
-// 65,536 inverses, profiles/r3e/ab.txt), so off.
-#ifndef FHE_INV64_E32
-#define FHE_INV64_E32 0
-#endif
+constexpr bool polymul_dual() { return gk_logn(LOGN) >= 12; }
+// Twiddle stages loaded ahead of a pass's exchange (ntt_core.hpp kPfSingle)
 template <int LOGN, typename W>
-constexpr int inv_key() { return (FHE_INV64_E32 && sizeof(W) == 8 && LOGN == 14) ? gk(LOGN, 5) : LOGN; }
-template <int LOGN, typename W>
-constexpr int polymul_key() {
-    if (sizeof(W) == 8) return (FHE_POLY64 == 2 && LOGN == 14) ? gk(LOGN, 5) : LOGN;
-    return (!FHE_POLY_E16 && sizeof(W) == 4 && LOGN >= 13 && LOGN <= 14) ? gk(LOGN, 5) : LOGN;
-}
+constexpr int polymul2_pf() { return sizeof(W) == 8 ? 0 : Geo<LOGN>::LOGE == 5 ? 1 : kPfPolymul; }
+// Where k_polymul parks fwd(a) while fwd(b) runs: 0 = VGPRs (N < 32), 1 = a
+// second LDS region (it fits at every N <= 2048).  Keeping both spectra in
+// VGPRs cost 150-255 VGPRs at the larger degrees.
 template <int LOGN>
-constexpr int polymul_pf() { return Geo<LOGN>::LOGE == 5 ? FHE_PF_POLY32 : kPfPolymul; }
-// 64-bit words at N = 16384: the dual kernel at 16 coefficients per thread
-// (two 16-word u64 spectra = 64 VGPRs; no stash of fwd(a) in LDS or HBM).
-#ifndef FHE_POLY_DUAL
-#define FHE_POLY_DUAL 1
-#endif
-#ifndef FHE_POLY_DUAL64
-#define FHE_POLY_DUAL64 1
-#endif
-#ifndef FHE_PF_DUAL64
-#define FHE_PF_DUAL64 0
-#endif
-// The 64-bit dual kernel also at N = 4096 / 8192 (16 per thread, one
-// workgroup per pair, occupancy floor 4 waves per SIMD; 123-126 VGPRs, no
-// spill): per 16,384 pairs at N = 8192 2.83 -> 2.23 ms (Q_60_1) and 2.75 ->
-// 2.10 ms (the 62-bit prime), at N = 4096 1.23 -> 1.06 ms (Q_60_1) (round 5).
-#ifndef FHE_POLY_DUAL64_SMALL
-#define FHE_POLY_DUAL64_SMALL 1
-#endif
-// The dual kernel also at N = 4096 with 16 per thread (one 256-thread
-// workgroup per pair, <= 128 VGPRs): 30.3 -> 28.1 us for C2's 1024 pairs,
-// 1.67 -> 1.49 ms (q < 2^27, lazy) and 1.74 -> 1.62 ms (q < 2^30) per 65,536
-// (round 5).  FHE_POLY_DUAL_E16=0 keeps the single-transform kernel.
-#ifndef FHE_POLY_DUAL_E16
-#define FHE_POLY_DUAL_E16 1
-#endif
-template <int LOGN, typename W>
-constexpr bool polymul_dual() {
+constexpr int polymul_stash() { return gk_logn(LOGN) < 5 ? 0 : 1; }
+
+// Raw pass-0 coefficients of a P == 1 polynomial (bit-reversed order), for
+// prefetching through a fwd_rest hook.
+template <int LOGN>
+__device__ __forceinline__ void load_raw(uint64_t (&raw)[Geo<LOGN>::E], uint32_t tau, const uint64_t *src) {
     using G = Geo<LOGN>;
-    if constexpr (sizeof(W) == 4)
-        return (G::LOGE == 5 && FHE_POLY_DUAL) || (FHE_POLY_DUAL_E16 && G::P == 1 && G::LOGE == 4 && G::L == 12);
-    else return FHE_POLY_DUAL64 && G::P == 1 && G::LOGE == 4 &&
-                ((G::L == 14 && FHE_POLY64 == 1) || (FHE_POLY_DUAL64_SMALL && (G::L == 12 || G::L == 13)));
+    const auto r = brsrc(src);
+#pragma unroll
+    for (int t = 0; t < G::E; ++t) raw[t] = bload(r, tau * 8u, cbrv(t, G::LOGE) * G::T * 8u);
 }
-template <int LOGN, typename W>
-constexpr int polymul2_pf() { return sizeof(W) == 8 ? FHE_PF_DUAL64 : polymul_pf<LOGN>(); }
 
 template <int LOGN, typename W, bool LAZY>
 __device__ __forceinline__ void polymul_body(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, uint64_t *c,
                                              size_t batch, const NttArgs<W> &A) {
     using G = Geo<LOGN>;
-    constexpr int STASH = polymul_stash<LOGN, W>();
+    static_assert(!polymul_dual<LOGN, W>() && G::LOGE <= 4, "N >= 4096 runs k_polymul2");
+    constexpr int STASH = polymul_stash<LOGN>();
+    static_assert(STASH == 0 || G::P * (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024, "stash does not fit in LDS");
     __shared__ W lds_all[G::P * lds_elems<LOGN, W>() + (STASH == 1 ? G::P * G::N : 0)];
     const uint32_t tau = threadIdx.x & (G::T - 1), pl = wg_poly<G>();
     const size_t poly = (size_t)blockIdx.x * G::P + pl;
@@ -182,52 +124,49 @@ __device__ __forceinline__ void polymul_body(const uint64_t *__restrict__ a, con
     W va[STASH == 0 ? G::E : 1];
     // P == 1: b's coefficients are loaded during fwd(a)'s last pass, so
     // their HBM latency overlaps it (one workgroup per CU has no other
-    // workgroup to hide it behind).
-    constexpr bool PRE = G::P == 1 && FHE_POLY_PREFETCH && STASH == 1;  // no registers to spare at STASH 2
+    // workgroup to hide it behind).  No degree that runs this kernel has
+    // P == 1 any more (N >= 4096 went to k_polymul2); the path stays because
+    // without the hook's captures six small-degree 64-bit instantiations
+    // schedule differently.
+    constexpr bool PRE = G::P == 1 && STASH == 1;
     uint64_t rb[PRE ? G::E : 1];
     auto hook = [&] {
         if constexpr (PRE) load_raw<LOGN>(*reinterpret_cast<uint64_t(*)[G::E]>(rb), tau, b + poly * G::N);
     };
-    fwd_poly<LOGN, LAZY, polymul_pf<LOGN>()>(lds, v, tau, a + poly * G::N, valid, A, 0, hook);
+    fwd_poly<LOGN, LAZY, kPfPolymul>(lds, v, tau, a + poly * G::N, valid, A, 0, hook);
 #pragma unroll
     for (int e = 0; e < G::E; ++e) {
         const W x = fwd_to_canon<LAZY>(v[e], A);  // canonical: times a raw output below
         const uint32_t gi = gidx<LOGN, G::NP - 1>(tau, e);  // own positions: no sync needed
         if constexpr (STASH == 0) va[e] = x;
-        else if constexpr (STASH == 1) st[gi] = x;
-        else if (valid) reinterpret_cast<W *>(crow)[gi] = x;  // W-typed: first half of c's row
+        else st[gi] = x;
     }
-    // keep b's raw loads (2 VGPRs per coefficient) out of the stash
-    // conversion (a 64-bit mad result per coefficient): interleaved, the two
-    // peak together and spill at 32 coefficients per thread
-    if constexpr (G::LOGE == 5) __builtin_amdgcn_sched_barrier(0);
     if constexpr (G::NP > 1) __syncthreads();  // LDS exchange buffer is reused by the second transform
     // opaque copy of the lane index (u64 path): stops the compiler from
     // keeping the first transform's address arithmetic live for reuse.  At
     // u32 the reuse is cheaper than recomputing (measured, r05 A/B).
     uint32_t tb = tau;
-    if constexpr (sizeof(W) == 8 || STASH == 2) asm volatile("" : "+v"(tb));
+    if constexpr (sizeof(W) == 8) asm volatile("" : "+v"(tb));
     if constexpr (PRE)
-        fwd_poly<LOGN, LAZY, polymul_pf<LOGN>()>(lds, v, tb, b + poly * G::N, valid, A, 0, NoHook{},
+        fwd_poly<LOGN, LAZY, kPfPolymul>(lds, v, tb, b + poly * G::N, valid, A, 0, NoHook{},
                                                reinterpret_cast<uint64_t(*)[G::E]>(rb));
     else
-        fwd_poly<LOGN, LAZY, polymul_pf<LOGN>()>(lds, v, tb, b + poly * G::N, valid, A);
+        fwd_poly<LOGN, LAZY, kPfPolymul>(lds, v, tb, b + poly * G::N, valid, A);
 #pragma unroll
     for (int e = 0; e < G::E; ++e) {
         const uint32_t gi = gidx<LOGN, G::NP - 1>(tb, e);
         W x;
         if constexpr (STASH == 0) x = va[e];
-        else if constexpr (STASH == 1) x = st[gi];
-        else x = valid ? reinterpret_cast<const W *>(crow)[gi] : W(0);
+        else x = st[gi];
         v[e] = A.ar.mont(x, v[e]);  // a*b*R^-1 in [0, 2q): canonical x raw v[e] (< R)
     }
     if constexpr (G::NP > 1) __syncthreads();
     uint32_t ti = tau;
-    if constexpr (sizeof(W) == 8 || STASH == 2) asm volatile("" : "+v"(ti));
-    inv_poly_from_regs<LOGN, polymul_pf<LOGN>()>(lds, v, ti, crow, valid, A, A.ninv_r);
+    if constexpr (sizeof(W) == 8) asm volatile("" : "+v"(ti));
+    inv_poly_from_regs<LOGN, kPfPolymul>(lds, v, ti, crow, valid, A, A.ninv_r);
 }
 template <int LOGN, typename W, bool LAZY>
-__global__ void __launch_bounds__(Geo<LOGN>::THREADS, (polymul_occ<LOGN, W>()))
+__global__ void __launch_bounds__(Geo<LOGN>::THREADS, 1)  // one transform's LDS plus the stash: no occupancy floor
 k_polymul(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, uint64_t *c, size_t batch,
           NttArgs<W> A) {
     polymul_body<LOGN, W, LAZY>(a, b, c, batch, A);
@@ -248,10 +187,6 @@ k_polymul_limbs(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, 
 // other's transforms.
 // A persistent grid (workgroups looping over pairs, with or without a phase
 // stagger or an L2 touch of the next pair) measured no faster (round 4).
-// lab only: 1 = HBM traffic without transforms, 2 = transforms without HBM
-#ifndef FHE_POLY_LAB
-#define FHE_POLY_LAB 0
-#endif
 template <int LOGN, typename W, bool LAZY>
 __device__ __forceinline__ void polymul2_one(W *lds, uint32_t tau, const uint64_t *__restrict__ a,
                                              const uint64_t *__restrict__ b, uint64_t *c, size_t poly,
@@ -268,7 +203,7 @@ __device__ __forceinline__ void polymul2_one(W *lds, uint32_t tau, const uint64_
 template <int LOGN, typename W>
 constexpr int polymul2_occ() {
     constexpr int o = Geo<LOGN>::template occ_waves<W>();
-    return (FHE_POLY_DUAL_E16 && Geo<LOGN>::LOGE == 4 && (sizeof(W) == 4 || gk_logn(LOGN) < 14) && o > 4) ? 4 : o;
+    return (Geo<LOGN>::LOGE == 4 && (sizeof(W) == 4 || gk_logn(LOGN) < 14) && o > 4) ? 4 : o;
 }
 template <int LOGN, typename W, bool LAZY>
 __global__ void __launch_bounds__(Geo<LOGN>::THREADS, (polymul2_occ<LOGN, W>()))
@@ -280,44 +215,6 @@ k_polymul2(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, uint6
     const uint32_t tau = threadIdx.x;
     const size_t poly = blockIdx.x;
     if (poly >= batch) return;
-#if FHE_POLY_LAB == 1
-    // lab: HBM traffic only (loads of a, b and the store of c, no transforms)
-    {
-        const auto ra = brsrc(a + poly * G::N), rb = brsrc(b + poly * G::N), rc = brsrc(c + poly * G::N);
-#pragma unroll
-        for (int ch = 0; ch < G::E; ch += 8) {
-            uint64_t x[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = bload(ra, tau * 8u, (ch + e) * G::T * 8u) ^ bload(rb, tau * 8u, (ch + e) * G::T * 8u);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) bstore(rc, tau * 8u, (ch + e) * G::T * 8u, x[e]);
-        }
-        return;
-    }
-#elif FHE_POLY_LAB == 2
-    // lab: transforms only (inputs from the lane index, no HBM traffic)
-    {
-        W v[G::E], vb[G::E];
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) {
-            v[e] = (W)((tau * 131u + e * 7919u + (uint32_t)poly) & 0x3FFFFFFu);
-            vb[e] = (W)((tau * 577u + e * 104729u) & 0x3FFFFFFu);
-        }
-        {
-            Tw<W> t0[PassTw<LOGN, 0>::COUNT];
-            load_tw<LOGN, 0>(tau, A.twf, t0);
-            fwd_pass<LOGN, 0, LAZY, W>(v, t0, A.ar);
-            fwd_pass<LOGN, 0, LAZY, W>(vb, t0, A.ar);
-        }
-        fwd_rest2<LOGN, 1, LAZY, polymul2_pf<LOGN, W>()>(lds, v, vb, tau, A.twf, A.ar);
-#pragma unroll
-        for (int e = 0; e < G::E; ++e) v[e] = A.ar.mont(fwd_to_canon<LAZY>(v[e], A), vb[e]);
-        __syncthreads();
-        inv_poly_from_regs<LOGN, polymul2_pf<LOGN, W>(), false>(lds, v, tau, c, true, A, A.ninv_r,
-            0, [&](uint32_t gi, uint64_t x) -> uint64_t { if (x == ~0ull) c[gi] = x; return x; });
-        return;
-    }
-#endif
     polymul2_one<LOGN, W, LAZY>(lds, tau, a, b, c, poly, A);
 }
 template <int LOGN, typename W, bool LAZY>
@@ -390,10 +287,11 @@ static hipError_t inv_one(const Plan &p, const NttArgs<W> &A, hipStream_t s, con
             return go(k_polymul<PK, W, false>, k_polymul_limbs<PK, W, false>, pblocks, GP::THREADS, a, b, c, batch);
         }
     }
-    constexpr int IK = inv_key<LOGN, W>();
-    using GI = Geo<IK>;
+    // (64-bit words at N = 16384 at 32 coefficients per thread, as the
+    // forward: 7.91 vs 7.62 ms per 65,536 inverses, profiles/r3e/ab.txt)
+    using GI = Geo<LOGN>;
     const size_t iblocks = (batch + GI::P - 1) / GI::P;
-    return go(k_ntt_inv<IK, W>, k_ntt_inv_limbs<IK, W>, iblocks, GI::THREADS, a, c, batch);
+    return go(k_ntt_inv<LOGN, W>, k_ntt_inv_limbs<LOGN, W>, iblocks, GI::THREADS, a, c, batch);
 }
 
 template <typename W>
@@ -448,8 +346,8 @@ hipError_t launch_inv(const Plan &p, const uint64_t *in, uint64_t *out, size_t b
     return inv_any(p, in, nullptr, out, batch);
 }
 hipError_t launch_polymul(const Plan &p, const uint64_t *a, const uint64_t *b, uint64_t *c, size_t batch) {
-    // The HBM stash writes fwd(a) into c before b is read: if c aliases b,
-    // transform b first (the pointwise product commutes).
+    // If c aliases b, transform b first (the pointwise product commutes):
+    // kept from the kernels that parked fwd(a) in c's row before reading b.
     if (p.logn > kMaxFusedLogN && !p.wide) return launch_big(p, 4, a, b, c, batch);
     if (c == b) { const uint64_t *t = a; a = b; b = t; }
     if (p.wide) return launch_wide(p, 4, a, b, c, batch);

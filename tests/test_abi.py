@@ -216,6 +216,35 @@ def test_kernel_scratch_budget():
     assert len(with_scratch) <= SCRATCH_CEILING, with_scratch
 
 
+# ---------------------------------------------------- compile-time switches
+# Every FHE_* name the kernel sources test in a preprocessor conditional.  The
+# first seven are the axes on which the shipped .hip units differ (each unit
+# sets them before its includes), the last two the diagnostics builds of
+# DESIGN.md.  A variant that lost its A/B is deleted, not parked behind a new
+# switch: adding a name here is a reviewed change, like SCRATCH_CEILING.
+COMPILE_SWITCHES = {
+    "FHE_NS", "FHE_U64_NOVCC", "FHE_MULHI64", "FHE_SPLIT_X64", "FHE_STREAM_TW2", "FHE_STREAM_DEPTH",
+    "FHE_OPAQUE_TW", "FHE_DEBUG_SLOTS", "FHE_BR_STAMPS",
+}
+
+
+def test_compile_switches_are_the_listed_ones():
+    import glob
+    import re
+
+    csrc = os.path.join(ROOT, "node-fhe-accelerate_amd", "csrc")
+    files = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))
+    assert files
+    found = {}
+    for path in files:
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    for name in re.findall(r"\bFHE_\w+", line):
+                        found.setdefault(name, f"{os.path.basename(path)}:{no}")
+    assert set(found) == COMPILE_SWITCHES, {n: w for n, w in found.items() if n not in COMPILE_SWITCHES}
+
+
 # ------------------------------------------------------------ config flags
 def test_env_defaults_python(monkeypatch):
     """FHE_NTT_MODE / FHE_GPU_DEVICES fill the context

@@ -33,7 +33,7 @@ def rnd(seed, q, *shape):
 
 
 # ------------------------------------------------------------ ciphertext multiply
-# (4096, P27) takes the VGPR-slot layout (FHE_CTMUL_PREFER_REGS); 64-bit words
+# (4096, P27) takes the VGPR-slot layout (one pair per workgroup); 64-bit words
 # at N = 4096 / 8192 / 16384 the paired kernel (round 5: also Q_60_1 at 8192)
 # (8192 / 16384, 1073643521): the non-lazy 32-bit paired kernel (q in (2^27, 2^30))
 @pytest.mark.parametrize("n,q", [(4, 17), (16, 97), (256, 7681), (1024, P27), (2048, P62), (4096, P27),
@@ -335,8 +335,9 @@ def test_br_pair_concurrent_contexts(fg, monkeypatch, serial, b):
     with FHE_BR_PAIR_SERIAL=0 they may interleave, and a pair that is not
     co-resident in time goes to the repair pass.  Either way both results
     are exact (vs the one-CU kernel, and rows vs the oracle).  At batch 40
-    the same on six CUs per ciphertext (k_br_multi: 2 x 240 workgroups), at
-    batch 64 in its dense form (two workgroups per CU: 2 x 384)."""
+    the same on six CUs per ciphertext (k_br_multi: 2 x 240 workgroups); at
+    batch 64 six per ciphertext no longer fit one per CU, so that case runs
+    k_br_pair (2 x 128 workgroups)."""
     import torch
 
     n, q, bl, lv, dim, k = 4096, Q60, 10, 3, 12, 1
@@ -510,7 +511,7 @@ def test_key_switch_split_vs_oracle(fg, q, bl, lv, in_dim, out_dim, b):
 
 @pytest.mark.parametrize("name,n,q,bl,lv", [("tfhe-128-balanced", 2048, Q50, 15, 2),
                                              ("tfhe-256-secure", 4096, Q60, 10, 3)])
-@pytest.mark.parametrize("b", [1, 5, 64])  # 64: tfhe-256 on the dense multi-CU form
+@pytest.mark.parametrize("b", [1, 5, 64])  # 64: too many for k_br_multi at one workgroup per CU, runs k_br_pair
 def test_bootstrap_presets_vs_oracle(fg, name, n, q, bl, lv, b):
     """fhe_bootstrap_batch (bootstrap_with_test_poly, bootstrap_engine.cpp:
     684-711: blind rotation on two CUs per ciphertext, sample extract, key
