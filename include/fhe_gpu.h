@@ -304,6 +304,74 @@ int fhe_ct_dot_batch(fhe_ctx *ctx, const uint64_t *a, const uint64_t *b, size_t 
 int fhe_ct_dot_ptrs(fhe_ctx *ctx, const uint64_t *const *a, const uint64_t *const *b, size_t count, int is_ntt,
                     int accumulate, uint64_t *out);
 
+/* ---- public-weight tallies (encryption.cpp:890-902, :809-852, :1327-1460) --
+ * The weighted tally whose weights are public (share counts, district
+ * multipliers, per-ballot masks): no degree-2 result, no relinearisation key.
+ *
+ * Integer weights: out[g][w] = sum_i ((cts[g][i][w] mod q) * (scalars[g][i]
+ * mod q) mod q) mod q over the polys * n words of a ciphertext, canonical --
+ * EncryptionEngine::multiply_scalar (:890-902; PolynomialRing::multiply_scalar,
+ * polynomial_ring.cpp:454-473) per ballot folded by add().  The products are
+ * canonical residues and mod_add is associative and commutative on them, so
+ * the words equal fhe_poly_mul_scalar_batch per ballot followed by
+ * fhe_ct_sum_batch bit for bit, in one pass over the ballots instead of
+ * three.  Words and scalars may be any u64; any odd q < 2^64 and any n the
+ * context takes run the same kernel.  The scalar is reduced and prepared once
+ * per ballot, not per word.  The ballots are split into slices as the plain
+ * tally's (FHE_TALLY_SPLIT=<S> forces the number, clamped to count).
+ * count == 0 fails with "Cannot add empty vector of ciphertexts".
+ * accumulate != 0 reads `out` as one more (unscaled) term.  `out` must not
+ * overlap an input (checked).
+ * fhe_ct_sum_scaled_batch  cts [groups][count][polys][n], polys 1..3, scalars
+ *   [groups][count] in the same residence as cts -> out [groups][polys][n].
+ *   FHE_HOST stages the ballots chunk by chunk and folds the chunks with the
+ *   accumulate flag.  A multi-device context splits the groups.  Device
+ *   ciphertext buffers must be 16-byte aligned.
+ * fhe_ct_sum_scaled_ptrs   cts is a HOST array of `count` DEVICE pointers
+ *   (polys * n words each, 16-byte aligned, may repeat), scalars a HOST array
+ *   of `count` u64; out is a device buffer.  Both are copied before the call
+ *   returns.  On a multi-device context the call runs on the device that holds
+ *   cts[0], and every pointer must be memory of that device.
+ *
+ * Plaintext-polynomial weights: out[g] = sum_i multiply_plain(cts[g][i],
+ * pts[g][i]) folded by add() = (sum_i c0_i (*) p_i, sum_i c1_i (*) p_i), with
+ * pts the already-encoded plaintext polynomials (any u64, read as x mod q).
+ * The inverse transform is a Z_q-linear map, so on canonical residues
+ *   sum_i multiply_plain(ct_i, p_i) = ( inv(sum C0_i P_i), inv(sum C1_i P_i) )
+ * holds bit for bit: three forward transforms per pair and two inverse
+ * transforms per slice of pairs, no intermediate ciphertext, and the words of
+ * fhe_polymul_batch of each component with the plaintext followed by
+ * fhe_ct_sum_batch (polys = 2).  is_ntt != 0: the ciphertexts and the result
+ * are NTT-domain, pts are still coefficient form and are forward-transformed
+ * (:819-821); no inverse runs, and the words are those of fhe_ntt_fwd_batch(pt)
+ * and fhe_pointwise_batch followed by fhe_ct_sum_batch.  The pairs are split
+ * into slices across the chip and the partial rows folded by the tally kernel;
+ * FHE_DOT_SPLIT=<S> forces the number of slices (read per call, clamped to
+ * count).  There is no by-component variant: FHE_DOT_COMPONENTS has no effect
+ * on these calls.  count == 0 fails with "Cannot tally empty ballot list".
+ * accumulate != 0 reads `out` as one more degree-1 term (any u64 words).
+ * `out` must not overlap an input.  Shapes outside the fused family
+ * (n > 16384, or q >= 2^62) run composed: chunks of batched transforms and
+ * pointwise products into a bounded temporary, each folded into `out` by the
+ * tally kernel -- bit-exact, not expected to be fast.
+ * fhe_ct_dot_plain_batch  cts [groups][count][2][n], pts [groups][count][n] ->
+ *   out [groups][2][n].  FHE_HOST stages chunks of pairs and folds them with
+ *   the accumulate flag.  A multi-device context splits the groups.  Device
+ *   buffers must be 16-byte aligned.
+ * fhe_ct_dot_plain_ptrs   cts, pts are HOST arrays of `count` DEVICE pointers
+ *   (2 n and n words, 16-byte aligned; pointers may repeat, one plaintext may
+ *   weigh several ballots); out is a device buffer.  The tables are copied
+ *   before the call returns.  On a multi-device context the call runs on the
+ *   device that holds cts[0], and every pointer must be memory of that device. */
+int fhe_ct_sum_scaled_batch(fhe_ctx *ctx, const uint64_t *cts, const uint64_t *scalars, uint32_t polys, size_t count,
+                            size_t groups, int accumulate, uint64_t *out, int where);
+int fhe_ct_sum_scaled_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, const uint64_t *scalars, uint32_t polys,
+                           size_t count, int accumulate, uint64_t *out);
+int fhe_ct_dot_plain_batch(fhe_ctx *ctx, const uint64_t *cts, const uint64_t *pts, size_t count, size_t groups,
+                           int is_ntt, int accumulate, uint64_t *out, int where);
+int fhe_ct_dot_plain_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, const uint64_t *const *pts, size_t count,
+                          int is_ntt, int accumulate, uint64_t *out);
+
 /* ---- TFHE bootstrapping pieces (bootstrap_engine.cpp) --------------------
  * GLWE [batch][k+1][n] as above; LWE masks [batch][dim], bodies [batch].
  * fhe_glwe_rotate_batch    multiply_glwe_by_monomial (:249-261) by X^rot[c].

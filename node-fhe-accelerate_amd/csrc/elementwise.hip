@@ -134,8 +134,7 @@ k_neg(const uint64_t *__restrict__ a, uint64_t *__restrict__ c, size_t n, uint64
 
 __device__ __forceinline__ uint64_t mulsc1(uint64_t x, uint64_t s, uint64_t sp, const ModConsts &m) {
     if (m.q >> 63) return mod128_slow(__umul64hi(x, s), x * s, m.q);
-    const uint64_t r = x * s - __umul64hi(x, sp) * m.q;  // Shoup, [0, 2q)
-    return r >= m.q ? r - m.q : r;
+    return shoup64(x, s, sp, m.q);
 }
 
 __global__ void __launch_bounds__(kBlock)

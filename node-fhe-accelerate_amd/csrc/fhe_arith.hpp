@@ -313,6 +313,14 @@ __device__ __forceinline__ uint64_t mod64_slow(uint64_t x, uint64_t q, uint64_t 
     return r >= q ? r - q : r;
 }
 
+// x * s mod q, canonical, for any u64 x, s < q < 2^63 and sp = floor(s 2^64 / q)
+// (Shoup): the difference is in [0, 2q).  multiply_scalar's word product
+// (elementwise.hip) and the scaled tally's (tally.hip).
+__device__ __forceinline__ uint64_t shoup64(uint64_t x, uint64_t s, uint64_t sp, uint64_t q) {
+    const uint64_t r = x * s - __umul64hi(x, sp) * q;
+    return r >= q ? r - q : r;
+}
+
 // Moduli up to 2^64 (ntt_wide.hip, the composed key MAC): a * b * 2^-64 mod q, canonical, for a, b < q and any odd q < 2^64:
 // (a b + m q) / 2^64 < 2q, and its 65th bit is the carry of the high sum.
 __device__ __forceinline__ uint64_t wmont(uint64_t a, uint64_t b, uint64_t q, uint64_t qinv) {

@@ -185,6 +185,29 @@ hipError_t launch_ml_montmul(const uint64_t consts[7], const uint64_t *a, const 
 // more term.  words even, q odd.
 hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
                          size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s);
+// Scaled ciphertext sum (tally.hip k_ct_sum_scaled): launch_ct_sum with ballot
+// i of group g multiplied by the scalar of table entry tab[g count + i] (16
+// bytes each, device memory).  launch_scalar_prep fills `total` entries from
+// raw u64 scalars on the device; scalar_entry is the same map on the host.
+hipError_t launch_scalar_prep(const ModConsts &m, const uint64_t *raw, void *tab, size_t total, hipStream_t s);
+hipError_t launch_ct_sum_scaled(const ModConsts &m, const void *src, bool ptr_table, const void *tab, uint64_t *out,
+                                size_t words, size_t count, size_t per, size_t slices, size_t groups, int accumulate,
+                                hipStream_t s);
+inline void scalar_entry(uint64_t raw, uint64_t q, uint64_t e[2]) {
+    const unsigned __int128 s = raw % q;
+    e[0] = (q >> 63) ? (uint64_t)((s << 64) % q) : (uint64_t)s;
+    e[1] = (q >> 63) ? 0 : (uint64_t)((s << 64) / q);
+}
+// Ciphertext inner product with public plaintext polynomials (dot_plain.hip):
+// cts [groups][count][2][n], pts [groups][count][n], or with ptr_table device
+// arrays of `count` pointers each (groups == 1); slices as launch_ct_dot, rows
+// dst [groups][slices][2][n], canonical.  The fused family only (n <= 16384,
+// q < 2^62).  is_ntt: the ciphertexts and the rows are NTT-domain, no
+// workspace.  Otherwise a workspace of ct_dot_plain_ws_bytes.
+size_t ct_dot_plain_resident(const Plan &p, int is_ntt);
+size_t ct_dot_plain_ws_bytes(const Plan &p, size_t slices, size_t groups);
+hipError_t launch_ct_dot_plain(const Plan &p, const void *cts, const void *pts, bool ptr_table, void *ws, uint64_t *dst,
+                               size_t count, size_t per, size_t slices, size_t groups, int is_ntt);
 // Ciphertext inner product (dot.hip).  a, b are [groups][count][2][n] u64, or
 // with ptr_table device arrays of `count` pointers to 2 n u64 each (groups ==
 // 1).  Slice y of `slices` covers pairs [y per, min(count, (y+1) per)) and

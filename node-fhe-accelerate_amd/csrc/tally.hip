@@ -106,4 +106,132 @@ hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, ui
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- public integer weights
+// k_ct_sum_scaled: out[g][w] = sum_i ((in[g][i][w] mod q) (s[g][i] mod q) mod q)
+// mod q -- multiply_scalar per ballot (encryption.cpp:890-902,
+// polynomial_ring.cpp:454-473) folded by add(): k_ct_sum with one product per
+// word.  The scalar is wave-uniform, so it is reduced and prepared once per
+// ballot (k_scalar_prep, or the host for pointer tables and host-resident
+// ballots) into a table of 16-byte entries that the kernel reads as scalar
+// loads:
+//   q < 2^63   {s mod q, floor((s mod q) 2^64 / q)}: mul_scalar's Shoup product
+//              (shoup64), exact for raw u64 words;
+//   q >= 2^63  {(s mod q) 2^64 mod q, 0}: the word, one conditional subtraction
+//              from canonical, times the Montgomery-form scalar by wmont --
+//              the canonical product with the carry bit, in place of
+//              mul_scalar's 128-step shift-subtract.
+// Products are canonical; they are summed and folded as k_ct_sum's words.  A
+// prior `out` (accumulate) is one more unscaled term.  The choice between the
+// two products is made once per kernel (WIDE), outside every loop: as a branch
+// per word the compiler ran the wmont product unconditionally beside the
+// Shoup one.
+template <bool WIDE>
+__device__ __forceinline__ uint64_t scaled1(uint64_t x, u64x2 s, const ModConsts &m) {
+    if constexpr (WIDE) return wmont(x >= m.q ? x - m.q : x, s.x, m.q, m.qinv);
+    else return shoup64(x, s.x, s.y, m.q);
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_scalar_prep(const uint64_t *__restrict__ raw, u64x2 *__restrict__ tab, size_t total, ModConsts m) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= total) return;
+    const uint64_t s = mod64_slow(raw[i], m.q, m.mu);
+    u64x2 e;
+    if (m.q >> 63) {
+        e.x = wmont(s, m.r2, m.q, m.qinv);
+        e.y = 0;
+    } else {  // floor(s 2^64 / q) by restoring division (s < q < 2^63: no carry)
+        uint64_t r = s, quo = 0;
+        for (int b = 0; b < 64; ++b) {
+            r <<= 1;
+            quo <<= 1;
+            if (r >= m.q) {
+                r -= m.q;
+                quo |= 1;
+            }
+        }
+        e.x = s;
+        e.y = quo;
+    }
+    tab[i] = e;
+}
+
+template <bool PTR, bool WIDE>
+__device__ __forceinline__ void ct_sum_scaled_body(const void *__restrict__ src, const u64x2 *__restrict__ tab,
+                                                   uint64_t *__restrict__ out, size_t cols, size_t count, size_t per,
+                                                   size_t groups, int accumulate, const ModConsts &m) {
+    const size_t i0 = (size_t)blockIdx.y * per;
+    const size_t i1 = i0 + per < count ? i0 + per : count;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t g = blockIdx.z; g < groups; g += gridDim.z) {
+        u64x2 *const dst = reinterpret_cast<u64x2 *>(out) + (g * gridDim.y + blockIdx.y) * cols;
+        const u64x2 *const sc = tab + g * count;
+        for (size_t col = (size_t)blockIdx.x * kBlock + threadIdx.x; col < cols; col += stride) {
+            auto row = [&](size_t i) -> const u64x2 * {
+                if (PTR) return reinterpret_cast<const u64x2 *const *>(src)[i] + col;
+                return reinterpret_cast<const u64x2 *>(src) + (g * count + i) * cols + col;
+            };
+            auto mul = [&](u64x2 v, size_t i) {
+                const u64x2 s = sc[i];
+                u64x2 p;
+                p.x = scaled1<WIDE>(v.x, s, m);
+                p.y = scaled1<WIDE>(v.y, s, m);
+                return p;
+            };
+            TallyAcc a;
+            if (accumulate) a.add(dst[col]);
+            size_t i = i0;
+            for (; i + kUnroll <= i1; i += kUnroll) {
+                u64x2 v[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) v[u] = __builtin_nontemporal_load(row(i + u));
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) a.add(mul(v[u], i + u));
+            }
+            for (; i < i1; ++i) a.add(mul(__builtin_nontemporal_load(row(i)), i));
+            u64x2 r;
+            r.x = fold128(a.hi0, a.lo0, m);
+            r.y = fold128(a.hi1, a.lo1, m);
+            dst[col] = r;
+        }
+    }
+}
+
+template <bool PTR>
+__global__ void __launch_bounds__(kBlock)
+k_ct_sum_scaled(const void *__restrict__ src, const u64x2 *__restrict__ tab, uint64_t *__restrict__ out, size_t cols,
+                size_t count, size_t per, size_t groups, int accumulate, ModConsts m) {
+    if (m.q >> 63) ct_sum_scaled_body<PTR, true>(src, tab, out, cols, count, per, groups, accumulate, m);
+    else ct_sum_scaled_body<PTR, false>(src, tab, out, cols, count, per, groups, accumulate, m);
+}
+
+hipError_t launch_scalar_prep(const ModConsts &m, const uint64_t *raw, void *tab, size_t total, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    if (!(m.q & 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scalar_prep, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, raw,
+                       reinterpret_cast<u64x2 *>(tab), total, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_ct_sum_scaled(const ModConsts &m, const void *src, bool ptr_table, const void *tab, uint64_t *out,
+                                size_t words, size_t count, size_t per, size_t slices, size_t groups, int accumulate,
+                                hipStream_t s) {
+    if (words == 0 || count == 0 || groups == 0) return hipSuccess;
+    if ((words & 1) || !(m.q & 1) || per == 0 || slices == 0 || slices > 65535 || (slices - 1) * per >= count ||
+        slices * per < count || (ptr_table && groups != 1) || (accumulate && slices != 1))
+        return hipErrorInvalidValue;
+    const size_t cols = words / 2;
+    size_t gx = (cols + kBlock - 1) / kBlock;
+    if (gx > 65535) gx = 65535;  // grid-stride beyond
+    const dim3 grid((unsigned)gx, (unsigned)slices, (unsigned)(groups < 65535 ? groups : 65535));
+    const u64x2 *t = reinterpret_cast<const u64x2 *>(tab);
+    if (ptr_table)
+        hipLaunchKernelGGL(k_ct_sum_scaled<true>, grid, dim3(kBlock), 0, s, src, t, out, cols, count, per, groups,
+                           accumulate, m);
+    else
+        hipLaunchKernelGGL(k_ct_sum_scaled<false>, grid, dim3(kBlock), 0, s, src, t, out, cols, count, per, groups,
+                           accumulate, m);
+    return hipGetLastError();
+}
+
 }  // namespace FHE_NS

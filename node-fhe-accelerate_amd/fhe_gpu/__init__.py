@@ -117,6 +117,10 @@ SIGNATURES = [
     ("fhe_ct_sum_ptrs", C.c_int, [vp, vp, C.c_uint32, C.c_size_t, C.c_int, vp]),
     ("fhe_ct_dot_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_int]),
     ("fhe_ct_dot_ptrs", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
+    ("fhe_ct_sum_scaled_batch", C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_int]),
+    ("fhe_ct_sum_scaled_ptrs", C.c_int, [vp, vp, vp, C.c_uint32, C.c_size_t, C.c_int, vp]),
+    ("fhe_ct_dot_plain_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, C.c_int]),
+    ("fhe_ct_dot_plain_ptrs", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
     ("fhe_ggsw_prepare", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int]),
     ("fhe_external_product_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
@@ -483,6 +487,75 @@ class NTTProcessor:
     def forward_ntt_mul(self, coeffs, w, out=None):
         """to_ntt(coeffs) then pointwise by w (config C3, fused)."""
         return self._binary(lib().fhe_ntt_fwd_mul_batch, coeffs, w, out)
+
+    # -- public integer weights
+    def sum_scaled(self, cts, scalars, out=None, accumulate: bool = False, grouped=None):
+        """sum_i cts[i] * scalars[i] over the ballot axis in one launch
+        (multiply_scalar per ballot folded by add()): cts [count, ..., n] with
+        scalars [count], or cts [groups, count, ..., n] with scalars
+        [groups, count]; `...` is empty or the 1..3 polynomials of a
+        ciphertext.  Shapes as sum_batch; words and scalars are any u64.
+        accumulate: `out` is one more (unscaled) term of each sum."""
+        cts = _as_u64(cts)
+        shape = tuple(cts.shape)
+        grouped = len(shape) == 4 if grouped is None else bool(grouped)
+        lead = 2 if grouped else 1
+        if len(shape) < lead + 1 or shape[-1] != self.degree:
+            raise FHEError(-5, "Coefficient count must equal polynomial degree")
+        groups, count = (shape[0], shape[1]) if grouped else (1, shape[0])
+        if not _is_tensor(scalars):
+            scalars = np.ascontiguousarray(np.asarray(scalars, dtype=np.uint64))
+            if _is_tensor(cts):
+                scalars = torch.from_numpy(scalars.view(np.int64)).to(cts.device)
+        if tuple(scalars.shape) != shape[:lead]:
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        polys = 1
+        for d in shape[lead:-1]:
+            polys *= d
+        oshape = ((groups,) if grouped else ()) + shape[lead:]
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = _empty(cts, oshape)
+        elif tuple(out.shape) != oshape:
+            raise FHEError(-9, f"out must have shape {list(oshape)}")
+        ba, bs, bo = _Buf(cts), _Buf(scalars), _Buf(out, True)
+        w = _where(ba, bs, bo)
+        self._bind_stream(w)
+        _check(lib().fhe_ct_sum_scaled_batch(self._h, ba.ptr, bs.ptr, polys, count, groups, int(bool(accumulate)),
+                                             bo.ptr, w))
+        return out
+
+    def sum_scaled_buffers(self, bufs, scalars, out=None, accumulate: bool = False):
+        """sum_scaled over separately allocated device tensors [..., n] of one
+        shape (1..3 polynomials each) and a host sequence of integer scalars;
+        a tensor may be listed twice."""
+        bufs = list(bufs)
+        scal = np.ascontiguousarray(np.asarray([int(s) & (2**64 - 1) for s in scalars], dtype=np.uint64))
+        if len(scal) != len(bufs):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if not bufs:
+            raise FHEError(-9, "Cannot add empty vector of ciphertexts")
+        shape = tuple(bufs[0].shape)
+        if not shape or shape[-1] != self.degree:
+            raise FHEError(-5, "Coefficient count must equal polynomial degree")
+        if any(tuple(b.shape) != shape for b in bufs):
+            raise FHEError(-9, "operand shapes differ")
+        polys = 1
+        for d in shape[:-1]:
+            polys *= d
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = torch.empty_like(bufs[0])
+        bs, bo = [_Buf(b) for b in bufs], _Buf(out, True)
+        if _where(bo, *bs) != FHE_DEVICE:
+            raise FHEError(-9, "sum_scaled_buffers takes device tensors (stack host arrays for sum_scaled)")
+        self._bind_stream(FHE_DEVICE)
+        table = (C.c_void_p * len(bs))(*[b.ptr for b in bs])
+        _check(lib().fhe_ct_sum_scaled_ptrs(self._h, table, scal.ctypes.data, polys, len(bs), int(bool(accumulate)),
+                                            bo.ptr))
+        return out
 
 
 class PolynomialRing(NTTProcessor):
@@ -1113,6 +1186,94 @@ class EncryptionEngine:
         t1 = (C.c_void_p * len(b1))(*[b.ptr for b in b1])
         t2 = (C.c_void_p * len(b2))(*[b.ptr for b in b2])
         _check(lib().fhe_ct_dot_ptrs(r._h, t1, t2, len(b1), int(bool(is_ntt)), int(bool(accumulate)), bo.ptr))
+        return out
+
+    def tally_scalar_weighted(self, cts, scalars, out=None):
+        """Public integer weights: sum_i multiply_scalar(cts[i], scalars[i])
+        folded by add(), in one launch.  cts [count, 2 | 3, n] (or a list of
+        them; a list of device tensors is read in place), scalars `count`
+        integers -> [2 | 3, n]."""
+        r = self.ring
+        if len(cts) != len(scalars):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if isinstance(cts, (list, tuple)):
+            if len(cts) == 0:
+                raise FHEError(-9, "Cannot add empty vector of ciphertexts")
+            if all(_is_tensor(c) for c in cts):
+                for c in cts:
+                    if len(c.shape) != 2 or c.shape[0] not in (2, 3):
+                        raise FHEError(-9, "ciphertexts must be [2, n] or [3, n]")
+                return r.sum_scaled_buffers(cts, scalars, out)
+            cts = np.stack([np.asarray(c, dtype=np.uint64) for c in cts])
+        cts = _as_u64(cts)
+        if len(cts.shape) != 3 or cts.shape[1] not in (2, 3):
+            raise FHEError(-9, "ciphertexts must be [count, 2, n] or [count, 3, n]")
+        if not _is_tensor(scalars):
+            scalars = np.asarray([int(s) & (2**64 - 1) for s in scalars], dtype=np.uint64)
+        return r.sum_scaled(cts, scalars, out, grouped=False)
+
+    def dot_plain(self, cts, pts, is_ntt: bool = False, out=None, accumulate: bool = False, grouped=None):
+        """Public plaintext-polynomial weights in one fused launch: the
+        degree-1 sum sum_i multiply_plain(cts[i], pts[i]) folded by add(), with
+        no intermediate ciphertexts.  cts [count, 2, n] and already-encoded
+        pts [count, n] -> [2, n], or [groups, count, 2, n] and
+        [groups, count, n] -> [groups, 2, n]; grouped=None reads a 4-d cts as
+        grouped.  is_ntt: cts and the result are NTT-domain, pts are still
+        coefficient form.  Words equal multiply_plain() followed by
+        batch_add().  accumulate: `out` is one more degree-1 term."""
+        r = self.ring
+        cts, pts = _as_u64(cts), _as_u64(pts)
+        shape = tuple(cts.shape)
+        grouped = len(shape) == 4 if grouped is None else bool(grouped)
+        lead = 2 if grouped else 1
+        if len(shape) != lead + 2 or shape[lead:] != (2, r.degree):
+            raise FHEError(-9, "ciphertexts must be [count, 2, n] or [groups, count, 2, n]")
+        if tuple(pts.shape) != shape[:lead] + (r.degree,):
+            raise FHEError(-9, "plaintexts must be [count, n] or [groups, count, n]")
+        groups, count = (shape[0], shape[1]) if grouped else (1, shape[0])
+        if count == 0:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        oshape = ((groups,) if grouped else ()) + (2, r.degree)
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = _empty(cts, oshape)
+        elif tuple(out.shape) != oshape:
+            raise FHEError(-9, f"out must have shape {list(oshape)}")
+        b1, b2, bo = _Buf(cts), _Buf(pts), _Buf(out, True)
+        w = _where(b1, b2, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_dot_plain_batch(r._h, b1.ptr, b2.ptr, count, groups, int(bool(is_ntt)),
+                                            int(bool(accumulate)), bo.ptr, w))
+        return out
+
+    def dot_plain_buffers(self, bufs, pts, is_ntt: bool = False, out=None, accumulate: bool = False):
+        """dot_plain over separately allocated device ciphertexts [2, n] and
+        plaintext polynomials [n]; a tensor may be listed twice (one plaintext
+        may weigh several ballots)."""
+        r = self.ring
+        bufs, pts = list(bufs), list(pts)
+        if len(bufs) != len(pts):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if not bufs:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        if any(tuple(b.shape) != (2, r.degree) for b in bufs):
+            raise FHEError(-9, "ciphertexts must be [2, n]")
+        if any(tuple(p.shape) != (r.degree,) for p in pts):
+            raise FHEError(-9, "plaintexts must be [n]")
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an out buffer")
+            out = torch.empty((2, r.degree), dtype=bufs[0].dtype, device=bufs[0].device)
+        elif tuple(out.shape) != (2, r.degree):
+            raise FHEError(-9, f"out must have shape {[2, r.degree]}")
+        b1, b2, bo = [_Buf(b) for b in bufs], [_Buf(p) for p in pts], _Buf(out, True)
+        if _where(bo, *b1, *b2) != FHE_DEVICE:
+            raise FHEError(-9, "dot_plain_buffers takes device tensors (stack host arrays for dot_plain)")
+        r._bind_stream(FHE_DEVICE)
+        t1 = (C.c_void_p * len(b1))(*[b.ptr for b in b1])
+        t2 = (C.c_void_p * len(b2))(*[b.ptr for b in b2])
+        _check(lib().fhe_ct_dot_plain_ptrs(r._h, t1, t2, len(b1), int(bool(is_ntt)), int(bool(accumulate)), bo.ptr))
         return out
 
     def tally_weighted_votes(self, ballots, weights, ek: EvaluationKey, relinearize: str = "each", out=None):

@@ -251,6 +251,16 @@ export interface FHEDotEngine extends FHETallyEngine {
   dotProduct(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
 }
 
+/** Tallies under public weights, one launch each and no relinearisation key.
+ * tallyScalarWeightedVotes: sum_i multiplyScalar(ballots[i], weights[i])
+ * (fhe_ct_sum_scaled_ptrs).  dotPlain: sum_i multiplyPlain(cts[i], pts[i]) over
+ * degree-1 ciphertexts (fhe_ct_dot_plain_ptrs).  Both are word-identical to
+ * the chain of multiplyScalar() / multiplyPlain() and add(). */
+export interface FHEPublicWeightEngine extends FHEDotEngine {
+  tallyScalarWeightedVotes(ballots: Ciphertext[], weights: bigint[], progress?: ProgressCallback): Promise<Ciphertext>;
+  dotPlain(cts: Ciphertext[], pts: Plaintext[], progress?: ProgressCallback): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -310,6 +320,8 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   tallyWeightedVotes(ballots: Ciphertext[], weights: Ciphertext[], ek: EvaluationKey,
     progress?: ProgressCallback, options?: TallyWeightedOptions): Promise<Ciphertext>;
   dotProduct(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  tallyScalarWeightedVotes(ballots: Ciphertext[], weights: bigint[], progress?: ProgressCallback): Promise<Ciphertext>;
+  dotPlain(cts: Ciphertext[], pts: Plaintext[], progress?: ProgressCallback): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension). */
   deviceBuffer(handle: unknown): DeviceBuffer | undefined;
 }
@@ -377,6 +389,16 @@ export declare class NttContext {
    * fused launch (fhe_ct_dot_ptrs). */
   dot(buffersA: DeviceBuffer[], buffersB: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): DeviceBuffer;
   dotAsync(buffersA: DeviceBuffer[], buffersB: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): Promise<DeviceBuffer>;
+  /** out = sum_i buffers[i] * scalars[i] (entries as sum(); scalars a host array of
+   * buffers.length words, copied by the call): one launch (fhe_ct_sum_scaled_ptrs). */
+  sumScaled(buffers: DeviceBuffer[], scalars: BigUint64Array, out: DeviceBuffer): DeviceBuffer;
+  sumScaledAsync(buffers: DeviceBuffer[], scalars: BigUint64Array, out: DeviceBuffer): Promise<DeviceBuffer>;
+  /** out (2 n words) = sum_i multiplyPlain(ctBuffers[i], ptBuffers[i]) over ciphertexts of
+   * 2 n words and encoded plaintext polynomials of n words; entries may repeat; out is none
+   * of them: one fused launch (fhe_ct_dot_plain_ptrs).  isNtt: the ciphertexts and out are
+   * NTT-domain, the plaintexts still coefficient form. */
+  dotPlain(ctBuffers: DeviceBuffer[], ptBuffers: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): DeviceBuffer;
+  dotPlainAsync(ctBuffers: DeviceBuffer[], ptBuffers: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): Promise<DeviceBuffer>;
   ctMultiply(ct1: Words, ct2: Words, out: Words, isNtt?: number): Words;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;

@@ -746,6 +746,91 @@ function makeEngineClass(native) {
       }
       return r;
     }
+    /** Public integer weights: sum_i multiplyScalar(ballots[i], weights[i])
+     *  folded by add(), in one launch (fhe_ct_sum_scaled_ptrs); the words
+     *  equal that chain's.  Checks in tallyVotes' order after the length
+     *  check; budget: multiplyScalar's - 1 per ballot, folded by tallyVotes'
+     *  tree rule; progress counts the count - 1 additions. */
+    async tallyScalarWeightedVotes(ballots, weights, progress) {
+      this._check();
+      if (!Array.isArray(ballots) || !Array.isArray(weights) || ballots.length !== weights.length) {
+        throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (ballots.length === 0) {
+        throw new FHEError('Cannot add empty vector of ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      const start = Date.now();
+      let level = ballots.map((b) => b.noiseBudget - 1);
+      while (level.length > 1) {
+        const next = [];
+        for (let i = 0; i + 1 < level.length; i += 2) next.push(Math.min(level[i], level[i + 1]) - 1);
+        if (level.length % 2 === 1) next.push(level[level.length - 1]);
+        level = next;
+      }
+      const r = await guard(async () => {
+        const f = this._sumInputs(ballots);
+        const scalars = new BigUint64Array(weights.length);
+        for (let i = 0; i < weights.length; i++) scalars[i] = u64(weights[i]);
+        const out = this._buf(f.comps * this._n);
+        await this._ctx.sumScaledAsync(f.bufs, scalars, out);
+        return this._ct(out, ballots[0].keyId, level[0], ballots[0].degree, { packed: f.packed });
+      });
+      const total = ballots.length - 1;
+      for (let i = 1; progress && i <= total; i++) {
+        progress({ stage: 'tally_scalar_weighted_votes', current: i, total, elapsedMs: Date.now() - start,
+          progressPercent: (i / total) * 100 });
+      }
+      return r;
+    }
+    /** Public plaintext weights: sum_i multiplyPlain(cts[i], pts[i]) as one
+     *  degree-1 ciphertext, in one fused launch (fhe_ct_dot_plain_ptrs); the
+     *  words equal the chain of multiplyPlain() and add().  The plaintexts
+     *  are encoded as multiplyPlain's (_encoded), one upload per distinct
+     *  Plaintext object.  Degree-1 ciphertexts only; every ciphertext shares
+     *  cts[0]'s key and representation; budget: multiplyPlain's - 2 per
+     *  ballot, folded by tallyVotes' tree rule; progress counts the pairs. */
+    async dotPlain(cts, pts, progress) {
+      this._check();
+      if (!Array.isArray(cts) || !Array.isArray(pts) || cts.length !== pts.length) {
+        throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (cts.length === 0) throw new FHEError('Cannot tally empty ballot list', FHEErrorCode.INVALID_PARAMETERS);
+      const start = Date.now(), total = cts.length;
+      const r = await guard(async () => {
+        const A = [], P = [], uploaded = new Map();
+        let level = [], packed = false;
+        for (let i = 0; i < total; i++) {
+          const a = this._rlwe(cts[i]);
+          if (a.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+          if (i > 0) {
+            this._sameKey(cts[0], cts[i], 'add');
+            if (cts[i].isNtt !== cts[0].isNtt) throw new FHEError('Cannot combine ciphertexts in different representations (NTT vs coefficient)', FHEErrorCode.INVALID_PARAMETERS);
+          }
+          let p = uploaded.get(pts[i]);
+          if (!p) {
+            p = this._upload(this._encoded(pts[i]));
+            uploaded.set(pts[i], p);
+          }
+          A.push(a.buf);
+          P.push(p);
+          packed = packed || a.packed;
+          level.push(cts[i].noiseBudget - 2);
+        }
+        while (level.length > 1) {
+          const next = [];
+          for (let i = 0; i + 1 < level.length; i += 2) next.push(Math.min(level[i], level[i + 1]) - 1);
+          if (level.length % 2 === 1) next.push(level[level.length - 1]);
+          level = next;
+        }
+        const out = this._buf(2 * this._n);
+        await this._ctx.dotPlainAsync(A, P, out, !!cts[0].isNtt);
+        return this._ct(out, cts[0].keyId, level[0], 1, { packed });
+      });
+      for (let i = 1; progress && i <= total; i++) {
+        progress({ stage: 'dot_plain', current: i, total, elapsedMs: Date.now() - start, progressPercent: (i / total) * 100 });
+      }
+      return r;
+    }
 
     // ---- multiplicative operations (encryption.cpp:737-980)
     async multiply(ct1, ct2) {
@@ -780,12 +865,20 @@ function makeEngineClass(native) {
     async multiplyRelin(ct1, ct2, ek) { return this.relinearize(await this.multiply(ct1, ct2), ek); }
     async square(ct) { return this.multiply(ct, ct); }
     async squareRelin(ct, ek) { return this.relinearize(await this.square(ct), ek); }
-    /** multiply_plain (:809-848): each component times encode(pt); budget - 2 */
+    /** multiply_plain (:809-848): each component times encode(pt); budget - 2.
+     *  A degree-1 ciphertext takes the fused plain dot with one pair (one
+     *  upload of encode(pt), three forward transforms); the words are those
+     *  of the polymul path, which degree-2 inputs keep. */
     async multiplyPlain(ct, pt) {
       this._check();
       return guard(async () => {
         const a = this._rlwe(ct), n = this._n;
         const enc = this._encoded(pt);
+        if (a.comps === 2) {
+          const out = this._buf(2 * n);
+          await this._ctx.dotPlainAsync([a.buf], [this._upload(enc)], out, false);
+          return this._ct(out, ct.keyId, ct.noiseBudget - 2, ct.degree, { packed: a.packed });
+        }
         const rep = this._buf(a.comps * n);
         for (let c = 0; c < a.comps; c++) rep.upload(enc, c * n);
         const out = this._buf(a.comps * n);

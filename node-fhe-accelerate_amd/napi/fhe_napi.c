@@ -986,6 +986,117 @@ static napi_value ctx_dot(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[2], k.argv, 3);
 }
 
+/* sumScaled(buffers[], scalars, out): out = sum_i buffers[i] * scalars[i]
+ * (fhe_ct_sum_scaled_ptrs: multiplyScalar per ballot folded by add), one
+ * launch.  Entries as sum(); scalars is a host BigUint64Array of
+ * buffers.length words, copied before the call returns. */
+static int run_sum_scaled(job *j) {
+    return fhe_ct_sum_scaled_ptrs(j->c, (const uint64_t *const *)j->owned, j->owned + j->batch, (uint32_t)j->v[0],
+                                  j->batch, 0, j->p[0]);
+}
+static napi_value ctx_sum_scaled(napi_env env, napi_callback_info info) {
+    static const char *usage = "sumScaled(buffers[], scalars, out): DeviceBuffers of this context, scalars a BigUint64Array";
+    call k;
+    if (call_begin(env, info, 3, &k)) return NULL;
+    bool is_arr = false;
+    uint32_t cnt = 0;
+    uint64_t *o, *sc;
+    size_t no, nsc;
+    if (k.argc < 3 || napi_is_array(env, k.argv[0], &is_arr) != napi_ok || !is_arr ||
+        napi_get_array_length(env, k.argv[0], &cnt) != napi_ok || get_u64_array(env, k.argv[1], &sc, &nsc) ||
+        arr_arg(env, &k, 2, &o, &no) || k.where != FHE_DEVICE)
+        return bad_args(env, usage), NULL;
+    if (nsc != cnt) return range_err(env, "Ballots and weights must have the same size");
+    if (cnt == 0) return range_err(env, "Cannot add empty vector of ciphertexts");
+    if (no % k.n || no / k.n < 1 || no / k.n > 3) return range_err(env, "a ciphertext has 1 to 3 polynomials");
+    uint64_t *tab = (uint64_t *)malloc((size_t)2 * cnt * sizeof *tab); /* cnt pointers, then cnt scalars */
+    dblock **blks = k.async ? (dblock **)malloc(cnt * sizeof *blks) : NULL;
+    if (!tab || (k.async && !blks)) {
+        free(tab);
+        free(blks);
+        napi_throw_error(env, "NATIVE_ERROR", "out of memory");
+        return NULL;
+    }
+    for (uint32_t i = 0; i < cnt; ++i) {
+        napi_value e;
+        dbuf *d = napi_get_element(env, k.argv[0], i, &e) == napi_ok ? unwrap_buf(env, e) : NULL;
+        if (!d || !d->blk || d->blk->owner != k.k || d->words != no || dbuf_ptr(d) == o) {
+            free(tab);
+            free(blks);
+            return bad_args(env, "sumScaled(buffers[], scalars, out): every entry a DeviceBuffer of out's size, none of them out"), NULL;
+        }
+        tab[i] = (uint64_t)(uintptr_t)dbuf_ptr(d);
+        if (blks) blks[i] = d->blk;
+    }
+    memcpy(tab + cnt, sc, (size_t)cnt * 8);
+    job *j = job_new(&k, run_sum_scaled, NULL);
+    j->owned = tab;
+    j->p[0] = o; j->v[0] = no / k.n; j->batch = cnt;
+    if (blks) {  /* pinned like the blocks of arr_arg (job_go) */
+        for (uint32_t i = 0; i < cnt; ++i) blks[i]->refs++;
+        j->xblks = blks;
+        j->nxblk = cnt;
+    }
+    return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+
+/* dotPlain(ctBuffers[], ptBuffers[], out, isNtt?): out = sum_i
+ * multiplyPlain(ct[i], pt[i]) (fhe_ct_dot_plain_ptrs), the degree-1 sum in one
+ * fused launch.  ct entries are DeviceBuffers of this context of 2 n words, pt
+ * entries of n words (encoded plaintext polynomials); entries may repeat; out
+ * has 2 n words and is none of them. */
+static int run_dot_plain(job *j) {
+    const uint64_t *const *tab = (const uint64_t *const *)j->owned;
+    return fhe_ct_dot_plain_ptrs(j->c, tab, tab + j->batch, j->batch, (int)j->v[0], 0, j->p[0]);
+}
+static napi_value ctx_dot_plain(napi_env env, napi_callback_info info) {
+    static const char *usage = "dotPlain(ctBuffers[], ptBuffers[], out, isNtt?): DeviceBuffers of this context";
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    bool arr_a = false, arr_b = false, is_ntt = false;
+    uint32_t cnt = 0, cnt_b = 0;
+    uint64_t *o;
+    size_t no;
+    if (k.argc < 3 || napi_is_array(env, k.argv[0], &arr_a) != napi_ok || !arr_a ||
+        napi_is_array(env, k.argv[1], &arr_b) != napi_ok || !arr_b ||
+        napi_get_array_length(env, k.argv[0], &cnt) != napi_ok ||
+        napi_get_array_length(env, k.argv[1], &cnt_b) != napi_ok || arr_arg(env, &k, 2, &o, &no) ||
+        k.where != FHE_DEVICE)
+        return bad_args(env, usage), NULL;
+    if (!undef_arg(env, &k, 3) && napi_get_value_bool(env, k.argv[3], &is_ntt) != napi_ok) return bad_args(env, usage), NULL;
+    if (cnt != cnt_b) return range_err(env, "Ballots and weights must have the same size");
+    if (cnt == 0) return range_err(env, "Cannot tally empty ballot list");
+    if (no != 2 * k.n) return range_err(env, "out holds a degree-1 ciphertext (2 polynomials)");
+    uint64_t **tab = (uint64_t **)malloc((size_t)2 * cnt * sizeof *tab);
+    dblock **blks = k.async ? (dblock **)malloc((size_t)2 * cnt * sizeof *blks) : NULL;
+    if (!tab || (k.async && !blks)) {
+        free(tab);
+        free(blks);
+        napi_throw_error(env, "NATIVE_ERROR", "out of memory");
+        return NULL;
+    }
+    for (uint32_t i = 0; i < 2 * cnt; ++i) {
+        napi_value e;
+        dbuf *d = napi_get_element(env, k.argv[i < cnt ? 0 : 1], i < cnt ? i : i - cnt, &e) == napi_ok ? unwrap_buf(env, e) : NULL;
+        if (!d || !d->blk || d->blk->owner != k.k || d->words != (i < cnt ? 2 : 1) * k.n || dbuf_ptr(d) == o) {
+            free(tab);
+            free(blks);
+            return bad_args(env, "dotPlain(ctBuffers[], ptBuffers[], out): ciphertexts of 2 n words, plaintexts of n words, none of them out"), NULL;
+        }
+        tab[i] = dbuf_ptr(d);
+        if (blks) blks[i] = d->blk;
+    }
+    job *j = job_new(&k, run_dot_plain, NULL);
+    j->owned = (uint64_t *)tab;
+    j->p[0] = o; j->v[0] = is_ntt ? 1 : 0; j->batch = cnt;
+    if (blks) {  /* pinned like the blocks of arr_arg (job_go) */
+        for (uint32_t i = 0; i < 2 * cnt; ++i) blks[i]->refs++;
+        j->xblks = blks;
+        j->nxblk = (size_t)2 * cnt;
+    }
+    return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+
 /* externalProduct(glwe, ggswCoeff, baseLog, level, out): k = 1, the key
  * prepared per call (host buffers: into host scratch; device: in place of
  * a stream-ordered temporary is not available here, so device callers use
@@ -1585,6 +1696,8 @@ static napi_value init(napi_env env, napi_value exports) {
         M("mulScalar", ctx_mul_scalar),
         M("sum", ctx_sum),
         M("dot", ctx_dot),
+        M("sumScaled", ctx_sum_scaled),
+        M("dotPlain", ctx_dot_plain),
         M("forwardMul", ctx_fwd_mul),
         M("externalProduct", ctx_ext_product),
         M("prepareGgsw", ctx_prep_ggsw),
