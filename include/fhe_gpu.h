@@ -229,6 +229,24 @@ int fhe_ct_multiply_relin_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level,
                                 const uint64_t *ct2, const uint64_t *rlk_ntt, uint64_t *out, size_t batch,
                                 int where);
 
+/* ---- ciphertext squaring and anomaly score (encryption.cpp:1004-1055, 1305-1321)
+ * EncryptionEngine::square / square_relin and compute_anomaly_score's
+ * relinearize(square(subtract(ballot, expected))).  The words equal
+ * fhe_ct_multiply_batch(d, d) with d = ct - ref from fhe_poly_sub_batch, bit
+ * for bit; input words may be any u64 (mod_sub's contract).  Coefficient form
+ * runs 2 forward + 3 inverse transforms in one kernel with the subtraction
+ * done while loading; is_ntt = 1 is one streaming pass.
+ * out[i] = square(ct[i] - ref[...]) : ct [batch][2][n] -> out [batch][3][n].
+ * ref == NULL, ref_count == 0: plain square.  ref_count == 1: one ciphertext for the whole batch.
+ * ref_count == batch: one per ciphertext.  Any other count: FHE_ERR_INVALID_ARG.
+ * out may not overlap ct or ref. */
+int fhe_ct_square_batch(fhe_ctx *ctx, const uint64_t *ct, const uint64_t *ref, size_t ref_count,
+                        uint64_t *out, size_t batch, int is_ntt, int where);
+/* relinearize(the above): out [batch][2][n]; coefficient form only, as fhe_ct_multiply_relin_batch */
+int fhe_ct_square_relin_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, const uint64_t *ct,
+                              const uint64_t *ref, size_t ref_count, const uint64_t *rlk_ntt,
+                              uint64_t *out, size_t batch, int where);
+
 /* ---- ciphertext tally (encryption.cpp:1061-1067, 1153-1168, 1327-1460) ---
  * EncryptionEngine::batch_add / batch_add_tree / tally_votes /
  * tally_multi_candidate: the sum of `count` ciphertexts of `polys` (1..3)

@@ -257,6 +257,46 @@ k_tensor_ntt(const uint64_t *__restrict__ x, const uint64_t *__restrict__ y, uin
     }
 }
 
+// EncryptionEngine::square for NTT-form ciphertexts (encryption.cpp:1027-1035
+// without the transforms): c0 = d0 d0, c1 = d0 d1 + d0 d1, c2 = d1 d1 with
+// k_tensor_ntt's reduction, d = x, or x - ref (mod_sub of any words) when
+// DIFF.  One 16-byte column of both components per lane and step: 16 B (+ the
+// ref's 16) read and 24 B written per coefficient.  n even, 16-byte aligned
+// buffers; ref_stride in words (0: one ref for the whole batch).
+template <bool DIFF>
+__global__ void __launch_bounds__(kBlock)
+k_square_ntt(const uint64_t *__restrict__ x, const uint64_t *__restrict__ ref, size_t ref_stride,
+             uint64_t *__restrict__ out, uint32_t n, size_t batch, ModConsts m) {
+    const uint32_t n2 = n / 2;
+    const size_t total = (size_t)n2 * batch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const size_t b = i / n2, k = i % n2;
+        const u64x2 *xr = reinterpret_cast<const u64x2 *>(x + 2 * b * n);
+        u64x2 d0 = __builtin_nontemporal_load(xr + k), d1 = __builtin_nontemporal_load(xr + n2 + k);
+        if constexpr (DIFF) {
+            const u64x2 *rr = reinterpret_cast<const u64x2 *>(ref + b * ref_stride);
+            const u64x2 r0 = rr[k], r1 = rr[n2 + k];
+            d0.x = addsub1(d0.x, r0.x, 1, m);
+            d0.y = addsub1(d0.y, r0.y, 1, m);
+            d1.x = addsub1(d1.x, r1.x, 1, m);
+            d1.y = addsub1(d1.y, r1.y, 1, m);
+        }
+        u64x2 c0, c1, c2;
+        c0.x = modmul1(d0.x, d0.x, m);
+        c0.y = modmul1(d0.y, d0.y, m);
+        const uint64_t tx = modmul1(d0.x, d1.x, m), ty = modmul1(d0.y, d1.y, m);
+        c1.x = addsub1(tx, tx, 0, m);
+        c1.y = addsub1(ty, ty, 0, m);
+        c2.x = modmul1(d1.x, d1.x, m);
+        c2.y = modmul1(d1.y, d1.y, m);
+        u64x2 *orow = reinterpret_cast<u64x2 *>(out + 3 * b * n);
+        __builtin_nontemporal_store(c0, orow + k);
+        __builtin_nontemporal_store(c1, orow + n2 + k);
+        __builtin_nontemporal_store(c2, orow + 2 * n2 + k);
+    }
+}
+
 // ---- composed external product / relinearisation (k > 1 or N > 16384) ----
 // out[b][j] = sum_r X[b][r] (.) G[r][kj(j)], X canonical NTT-domain digit
 // transforms, G prepared keys (NTT x R, R = 2^word): Montgomery products
@@ -350,6 +390,16 @@ hipError_t launch_tensor_ntt(const ModConsts &m, const uint64_t *x, const uint64
                              size_t batch, hipStream_t s) {
     if (batch == 0) return hipSuccess;
     hipLaunchKernelGGL(k_tensor_ntt, dim3(grid_for((size_t)n * batch)), dim3(kBlock), 0, s, x, y, out, n, batch, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_square_ntt(const ModConsts &m, const uint64_t *x, const uint64_t *ref, size_t ref_stride,
+                             uint64_t *out, uint32_t n, size_t batch, hipStream_t s) {
+    if (batch == 0) return hipSuccess;
+    if ((n & 1) || (((uintptr_t)x | (uintptr_t)ref | (uintptr_t)out) & 15)) return hipErrorInvalidValue;
+    const dim3 grid(grid_for((size_t)(n / 2) * batch)), block(kBlock);
+    if (ref) hipLaunchKernelGGL(k_square_ntt<true>, grid, block, 0, s, x, ref, ref_stride, out, n, batch, m);
+    else hipLaunchKernelGGL(k_square_ntt<false>, grid, block, 0, s, x, ref, ref_stride, out, n, batch, m);
     return hipGetLastError();
 }
 

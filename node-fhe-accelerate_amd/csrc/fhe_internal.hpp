@@ -123,6 +123,12 @@ hipError_t launch_cmux(const Plan &p, int k1, int level, int base_log, const uin
                        const uint64_t *ct1, uint64_t *out, size_t batch);
 // Ciphertext multiply (coefficient form): x, y [batch][2][n] -> out [batch][3][n]
 hipError_t launch_ct_mul(const Plan &p, const uint64_t *x, const uint64_t *y, uint64_t *out, size_t batch);
+// Ciphertext square (ct_square.hip, coefficient form, the fused family only):
+// out[i] = multiply(d, d) with d = ct[i], or ct[i] - ref[i ref_stride / 2n]
+// when ref != nullptr (ref_stride in words: 0 shares one ref, 2 n is one per
+// ciphertext).  ct [batch][2][n] -> out [batch][3][n].
+hipError_t launch_ct_square(const Plan &p, const uint64_t *ct, const uint64_t *ref, size_t ref_stride, uint64_t *out,
+                            size_t batch);
 
 // EncryptionEngine encrypt / decrypt / add_plain (ntt_engine.hip); keys
 // prepared NTT x R (Montgomery form): pk_prep (pk.a, pk.b), sk_prep (s, s^2).
@@ -226,6 +232,11 @@ hipError_t launch_ct_dot_ntt(const ModConsts &m, const void *a, const void *b, b
 // Tensor product of NTT-form ciphertexts: x, y [batch][2][n] -> [batch][3][n]
 hipError_t launch_tensor_ntt(const ModConsts &m, const uint64_t *x, const uint64_t *y, uint64_t *out, uint32_t n,
                              size_t batch, hipStream_t s);
+// Square of NTT-form ciphertexts, of x - ref when ref != nullptr (ref_stride
+// in words, 0 shares one ref): x [batch][2][n] -> [batch][3][n]; n even and
+// 16-byte aligned buffers, hipErrorInvalidValue otherwise.
+hipError_t launch_square_ntt(const ModConsts &m, const uint64_t *x, const uint64_t *ref, size_t ref_stride,
+                             uint64_t *out, uint32_t n, size_t batch, hipStream_t s);
 // GLWE rotation by X^r (multiply_glwe_by_monomial): polys per ciphertext =
 // k1; r = rot[c], or when rot == nullptr r = -(int32)((b[c]*2N + q/2)/q)
 // (blind_rotate's initial rotation by the LWE body).

@@ -923,6 +923,75 @@ __device__ __forceinline__ void fwd_poly2(W *lds, W (&v)[Geo<LOGN>::E], W (&v2)[
     fwd_rest2<LOGN, 1, LAZY, PF>(lds, v, v2, tau, twf, A.ar);
 }
 
+// E coefficients of the difference (a mod q) - (b mod q) mod q of two
+// polynomials, subtracted word by word as they arrive: canonical results.
+// CH pairs of raw words are in flight at a time; a pair with a word >= q is
+// loaded again and reduced in the (cold) slow path, as load_coeffs_chunked.
+template <int E, int CH, typename W, typename RD, typename FA, typename FB>
+__device__ __forceinline__ void load_diff_chunked(W (&v)[E], W q, RD &&red, FA &&a_of, FB &&b_of) {
+    static_assert(E % CH == 0, "whole chunks");
+#pragma unroll
+    for (int c = 0; c < E / CH; ++c) {
+        uint64_t ra[CH], rb[CH];
+#pragma unroll
+        for (int t = 0; t < CH; ++t) {
+            ra[t] = a_of(c * CH + t);
+            rb[t] = b_of(c * CH + t);
+        }
+        uint32_t bad = 0;
+#pragma unroll
+        for (int t = 0; t < CH; ++t) {
+            bad |= uint32_t((ra[t] >= (uint64_t)q) | (rb[t] >= (uint64_t)q)) << t;
+            const W x = W(ra[t]), y = W(rb[t]);
+            v[c * CH + t] = x - y + (x < y ? q : W(0));
+        }
+        if (__builtin_expect(bad != 0, 0)) {
+#pragma unroll
+            for (int t = 0; t < CH; ++t)
+                if ((bad >> t) & 1) {
+                    const W x = W(red(a_of(c * CH + t))), y = W(red(b_of(c * CH + t)));
+                    v[c * CH + t] = x - y + (x < y ? q : W(0));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// fwd_poly of the difference src - ref (the loader above in place of pass
+// 0's load; no R-scaling, no sub-transform offsets, no raw words handed in).
+template <int LOGN, bool LAZY, int PF, typename W>
+__device__ __forceinline__ void fwd_poly_diff(W *lds, W (&v)[Geo<LOGN>::E], uint32_t tau,
+                                              const uint64_t *__restrict__ src, const uint64_t *__restrict__ ref,
+                                              bool valid, const NttArgs<W> &A) {
+    using G = Geo<LOGN>;
+    constexpr bool ST = stream_tw<LOGN, W>();
+    constexpr int CH = G::E < 8 ? G::E : 8;
+    const Tw<W> *const twf = opaque_tw(A.twf);
+    Tw<W> t0[PassTw<LOGN, 0>::COUNT];
+    if constexpr (!ST) load_tw<LOGN, 0>(tau, twf, t0);
+    if constexpr (G::P == 1) {  // the caller has returned early if !valid
+        const auto ra = brsrc(src), rb = brsrc(ref);
+        const uint32_t vo = tau * 8u;
+        load_diff_chunked<G::E, CH>(
+            v, A.ar.q, SlowRed<W>{A}, [&](int t) -> uint64_t { return bload(ra, vo, cbrv(t, G::LOGE) * G::T * 8u); },
+            // ref may be shared by the whole batch: not streamed
+            [&](int t) -> uint64_t { return bload<0>(rb, vo, cbrv(t, G::LOGE) * G::T * 8u); });
+    } else {
+        load_diff_chunked<G::E, CH>(
+            v, A.ar.q, SlowRed<W>{A},
+            [&](int t) -> uint64_t { return valid ? __builtin_nontemporal_load(src + tau + cbrv(t, G::LOGE) * G::T) : 0; },
+            [&](int t) -> uint64_t { return valid ? ref[tau + cbrv(t, G::LOGE) * G::T] : 0; });
+    }
+    if constexpr (ST) {
+        stream_begin<LOGN, 0, false, false>(tau, twf, t0);
+        fwd_pass_stream<LOGN, 0, LAZY, false>(tau, v, t0, twf, A.ar);
+    } else {
+        fwd_pass<LOGN, 0, LAZY, W>(v, t0, A.ar);
+    }
+    fwd_rest<LOGN, 1, LAZY, PF>(lds, v, tau, twf, A.ar);
+}
+
 // Inverse transform from v (last-pass layout, values in [0, 2q)) to HBM
 // (bit-reversed store, coalesced), canonical output.  scale = N^-1 or
 // N^-1 * R, folded into the last stage.

@@ -139,6 +139,9 @@ SIGNATURES = [
     ("fhe_relinearize_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_ct_multiply_relin_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_square_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]),
+    ("fhe_ct_square_relin_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_glwe_rotate_batch", C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_cmux_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_blind_rotate_batch", C.c_int,
@@ -1383,6 +1386,58 @@ class EncryptionEngine:
         _check(lib().fhe_ct_multiply_relin_batch(r._h, ek.decomp_base_log, ek.level, b1.ptr, b2.ptr,
                                                  bk.ptr if ek.level else None, bo.ptr, nb, w))
         return out
+
+    def _expected(self, cts, expected):
+        """(buffer, ref_count) of the `expected` argument of the squaring
+        methods: None, one ciphertext [2, n] for all, or the shape of cts."""
+        if expected is None:
+            return None, 0
+        expected = _as_u64(expected)
+        if tuple(expected.shape) == (2, self.ring.degree):
+            return _Buf(expected), 1
+        if tuple(expected.shape) != tuple(cts.shape):
+            raise FHEError(-9, "ciphertext shapes differ")
+        return _Buf(expected), _lead(cts, (2, self.ring.degree))
+
+    def squared_difference(self, cts, expected, is_ntt: bool = False, out=None):
+        """square(subtract(ct, expected)) (:1004-1035 after :692-714) in one
+        kernel -> [..., 3, n]; expected is one ciphertext [2, n] shared by all
+        of cts, or one per ciphertext (the shape of cts).  The words equal
+        multiply(d, d) of d = subtract(cts, expected)."""
+        r = self.ring
+        cts = _as_u64(cts)
+        nb = _lead(cts, (2, r.degree))
+        be, cnt = self._expected(cts, expected)
+        if out is None:
+            out = _empty(cts, tuple(cts.shape[:-2]) + (3, r.degree))
+        bc, bo = _Buf(cts), _Buf(out, True)
+        w = _where(bc, be, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_square_batch(r._h, bc.ptr, be.ptr if be else None, cnt, bo.ptr, nb, int(bool(is_ntt)), w))
+        return out
+
+    def square(self, ct, is_ntt: bool = False, out=None):
+        """square (:1004-1035): 2 forward + 3 inverse transforms -> [..., 3, n]."""
+        return self.squared_difference(ct, None, is_ntt, out)
+
+    def compute_anomaly_score(self, cts, expected, ek: EvaluationKey, out=None):
+        """compute_anomaly_score (:1305-1321): relinearize(square(subtract(ct,
+        expected))) -> [..., 2, n]; expected as in squared_difference."""
+        r = self.ring
+        cts = _as_u64(cts)
+        nb = _lead(cts, (2, r.degree))
+        be, cnt = self._expected(cts, expected)
+        out = _like(cts) if out is None else out
+        bc, bk, bo = _Buf(cts), _Buf(ek.rlk_ntt), _Buf(out, True)
+        w = _where(bc, be, bo) if not ek.level else _where(bc, be, bk, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_square_relin_batch(r._h, ek.decomp_base_log, ek.level, bc.ptr, be.ptr if be else None, cnt,
+                                               bk.ptr if ek.level else None, bo.ptr, nb, w))
+        return out
+
+    def square_relin(self, ct, ek: EvaluationKey, out=None):
+        """square_relin (:1037-1055)."""
+        return self.compute_anomaly_score(ct, None, ek, out)
 
 
 class BootstrapEngine:

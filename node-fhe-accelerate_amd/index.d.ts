@@ -261,6 +261,14 @@ export interface FHEPublicWeightEngine extends FHEDotEngine {
   dotPlain(cts: Ciphertext[], pts: Plaintext[], progress?: ProgressCallback): Promise<Ciphertext>;
 }
 
+/** Fraud scoring (EncryptionEngine::compute_anomaly_score, encryption.cpp:
+ * 1305-1321): relinearize(square(subtract(ballot, expected))) in one call
+ * (fhe_ct_square_relin_batch; the subtraction happens while the squaring kernel
+ * loads), word-identical to that chain, with its key checks and noise budget. */
+export interface FHEAnomalyEngine extends FHEPublicWeightEngine {
+  computeAnomalyScore(ballot: Ciphertext, expected: Ciphertext, ek: EvaluationKey): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -322,6 +330,7 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   dotProduct(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
   tallyScalarWeightedVotes(ballots: Ciphertext[], weights: bigint[], progress?: ProgressCallback): Promise<Ciphertext>;
   dotPlain(cts: Ciphertext[], pts: Plaintext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  computeAnomalyScore(ballot: Ciphertext, expected: Ciphertext, ek: EvaluationKey): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension). */
   deviceBuffer(handle: unknown): DeviceBuffer | undefined;
 }
@@ -400,6 +409,14 @@ export declare class NttContext {
   dotPlain(ctBuffers: DeviceBuffer[], ptBuffers: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): DeviceBuffer;
   dotPlainAsync(ctBuffers: DeviceBuffer[], ptBuffers: DeviceBuffer[], out: DeviceBuffer, isNtt?: boolean): Promise<DeviceBuffer>;
   ctMultiply(ct1: Words, ct2: Words, out: Words, isNtt?: number): Words;
+  /** out [batch][3][n] = square(ct - ref) of ct [batch][2][n] (fhe_ct_square_batch); ref: null,
+   * one ciphertext [2][n] for the whole batch, or one per ciphertext; out overlaps neither. */
+  ctSquare(ct: Words, ref: Words | null, out: Words, isNtt?: number): Words;
+  ctSquareAsync(ct: Words, ref: Words | null, out: Words, isNtt?: number): Promise<Words>;
+  /** out [batch][2][n] = relinearize(ctSquare(ct, ref)) with a key from prepareRelinKey
+   * (fhe_ct_square_relin_batch); coefficient form. */
+  ctSquareRelinPrepared(ct: Words, ref: Words | null, rlkPrep: Words, baseLog: number, out: Words): Words;
+  ctSquareRelinPreparedAsync(ct: Words, ref: Words | null, rlkPrep: Words, baseLog: number, out: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;
@@ -445,6 +462,7 @@ export declare class PolynomialEngine {
   forwardMultiply(a: Words, w: Words, out?: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out?: Words): Words;
   ctMultiply(ct1: Words, ct2: Words, opts?: { isNtt?: boolean }, out?: Words): Words;
+  ctSquare(ct: Words, ref?: Words | null, opts?: { isNtt?: boolean }, out?: Words): Words;
   relinearize(ct3: Words, rlk: Words, baseLog?: number, out?: Words): Words;
   multiplyRelin(ct1: Words, ct2: Words, rlk: Words, baseLog?: number): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

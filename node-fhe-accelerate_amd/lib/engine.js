@@ -863,8 +863,60 @@ function makeEngineClass(native) {
       });
     }
     async multiplyRelin(ct1, ct2, ek) { return this.relinearize(await this.multiply(ct1, ct2), ek); }
-    async square(ct) { return this.multiply(ct, ct); }
-    async squareRelin(ct, ek) { return this.relinearize(await this.square(ct), ek); }
+    /** square (:1004-1050) in its own kernel (fhe_ct_square_batch: 2 forward
+     *  + 3 inverse transforms); words, budget and checks of multiply(ct, ct) */
+    async square(ct) {
+      this._check();
+      return guard(async () => {
+        const a = this._rlwe(ct);
+        if (a.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+        const out = this._buf(3 * this._n);
+        await this._ctx.ctSquareAsync(a.buf, null, out, ct.isNtt ? 1 : 0);
+        const red = Math.log2(this._n) + 5;
+        return this._ct(out, ct.keyId, ct.noiseBudget - red, 2, { packed: a.packed });
+      });
+    }
+    /** relinearize(square(ct - ref)) in one call (fhe_ct_square_relin_batch);
+     *  ref: the state of a second ciphertext, or null */
+    async _squareRelin(ct, a, ref, ek, budget, packed) {
+      const e = this._st(ek, 'EvaluationKey');
+      if (ct.keyId !== ek.keyId) throw new FHEError('Evaluation key does not match ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      const out = this._buf(2 * this._n);
+      await this._ctx.ctSquareRelinPreparedAsync(a.buf, ref ? ref.buf : null, e.prep, e.baseLog, out);
+      return this._ct(out, ct.keyId, budget, 1, { packed });
+    }
+    /** square_relin (:1052-1055): checks and budget of relinearize(square(ct)) */
+    async squareRelin(ct, ek) {
+      this._check();
+      if (ct && ct.isNtt) return this.relinearize(await this.square(ct), ek);  // relinearisation is coefficient form
+      return guard(async () => {
+        const a = this._rlwe(ct);
+        if (a.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+        const red = Math.log2(this._n) + 5;
+        return this._squareRelin(ct, a, null, ek, ct.noiseBudget - red - 1, a.packed);
+      });
+    }
+    /** compute_anomaly_score (:1305-1321): relinearize(square(subtract(ballot,
+     *  expected))) with the subtraction done while the kernel loads; checks in
+     *  that chain's order, its words and its budget (subtract's - 1, square's
+     *  - (log2 n + 5), relinearize's - 1) */
+    async computeAnomalyScore(ballot, expected, ek) {
+      this._check();
+      if (ballot && ballot.isNtt) {
+        const d = await this.subtract(ballot, expected);
+        return this.relinearize(await this.multiply(d, d), ek);
+      }
+      return guard(async () => {
+        const a = this._rlwe(ballot), b = this._rlwe(expected);
+        this._sameKey(ballot, expected, 'subtract');
+        if (ballot.isNtt !== expected.isNtt) throw new FHEError('Cannot combine ciphertexts in different representations (NTT vs coefficient)', FHEErrorCode.INVALID_PARAMETERS);
+        if (a.comps !== b.comps) throw new FHEError('ciphertext degrees differ', FHEErrorCode.INVALID_PARAMETERS);
+        if (a.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+        const red = Math.log2(this._n) + 5;
+        const budget = Math.min(ballot.noiseBudget, expected.noiseBudget) - 1 - red - 1;
+        return this._squareRelin(ballot, a, b, ek, budget, a.packed || b.packed);
+      });
+    }
     /** multiply_plain (:809-848): each component times encode(pt); budget - 2.
      *  A degree-1 ciphertext takes the fused plain dot with one pair (one
      *  upload of encode(pt), three forward transforms); the words are those

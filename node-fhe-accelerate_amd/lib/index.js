@@ -43,6 +43,11 @@ class PolynomialEngine {
   ctMultiply(ct1, ct2, { isNtt = false } = {}, out = new BigUint64Array(ct1.length / 2 * 3)) {
     return this.ctx.ctMultiply(ct1, ct2, out, isNtt ? 1 : 0);
   }
+  /** EncryptionEngine::square of ct - ref (ref: null, one ciphertext [2][n]
+   *  for the batch, or the shape of ct): ct [batch][2][n] -> [batch][3][n] */
+  ctSquare(ct, ref = null, { isNtt = false } = {}, out = new BigUint64Array(ct.length / 2 * 3)) {
+    return this.ctx.ctSquare(ct, ref, out, isNtt ? 1 : 0);
+  }
   /** EncryptionEngine::relinearize: ct3 [batch][3][n], rlk [level][2][n] (a_l, b_l) */
   relinearize(ct3, rlk, baseLog = 4, out = new BigUint64Array(ct3.length / 3 * 2)) {
     return this.ctx.relinearize(ct3, rlk, baseLog, out);
@@ -256,7 +261,9 @@ class GpuFHEEngine {
   async multiply(ct1, ct2, { isNtt = false } = {}) {
     return this.ctx.ctMultiplyAsync(ct1, ct2, this._alloc(ct1.length / 2 * 3), isNtt ? 1 : 0);
   }
-  async square(ct) { return this.multiply(ct, ct); }
+  async square(ct, { isNtt = false } = {}) {
+    return this.ctx.ctSquareAsync(ct, null, this._alloc(ct.length / 2 * 3), isNtt ? 1 : 0);
+  }
   /** ct: degree-2 ciphertexts [batch][3][n]; ek: generateEvalKey's key or a
    *  BigUint64Array [level][2][n] of (a_l, b_l).  { degree: 1 } returns a
    *  copy, as the reference does for a degree-1 input (encryption.cpp:906-909). */

@@ -1246,6 +1246,56 @@ static napi_value ctx_relin_prepared(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[3], k.argv, 4);
 }
 
+/* ctSquare(ct, ref | null, out, isNtt?): out = square(ct - ref), ct
+ * [batch][2][n] -> out [batch][3][n]; ref is one ciphertext [2][n] for the
+ * whole batch or one per ciphertext (EncryptionEngine::square, encryption.cpp:
+ * 1004-1035; compute_anomaly_score's square(subtract()), :1305-1321) */
+static int run_ct_square(job *j) {
+    return fhe_ct_square_batch(j->c, j->p[0], j->p[1], (size_t)j->v[1], j->p[2], j->batch, (int)j->v[0], j->where);
+}
+static napi_value ctx_ct_square(napi_env env, napi_callback_info info) {
+    static const char *usage = "ctSquare(ct, ref | null, out, isNtt?)";
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    uint64_t *x, *r = NULL, *o, is_ntt = 0;
+    size_t nx, nr = 0, no;
+    if (arr_arg(env, &k, 0, &x, &nx) || (!undef_arg(env, &k, 1) && arr_arg(env, &k, 1, &r, &nr)) ||
+        arr_arg(env, &k, 2, &o, &no) || (!undef_arg(env, &k, 3) && num_arg(env, &k, 3, &is_ntt)))
+        return bad_args(env, usage), NULL;
+    const size_t per = 2 * k.n;
+    if (nx % per || no != nx / 2 * 3) return range_err(env, "ciphertexts must be [batch][2][n], out [batch][3][n]");
+    if (r && nr != per && nr != nx) return range_err(env, "ref must be one ciphertext [2][n] or the shape of ct");
+    job *j = job_new(&k, run_ct_square, NULL);
+    j->p[0] = x; j->p[1] = r; j->p[2] = o; j->v[0] = is_ntt; j->v[1] = r ? nr / per : 0; j->batch = nx / per;
+    napi_value keep[3] = {k.argv[0], k.argv[2], k.argv[1]};  /* a null ref is not kept */
+    return job_go(env, &k, j, k.argv[2], keep, r ? 3 : 2);
+}
+/* ctSquareRelinPrepared(ct, ref | null, rlkPrep [level][2][n], baseLog, out):
+ * relinearize(ctSquare(ct, ref)), out [batch][2][n] (square_relin :1037-1055) */
+static int run_ct_square_relin(job *j) {
+    return fhe_ct_square_relin_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], j->p[0], j->p[1], (size_t)j->v[2],
+                                     j->v[1] ? j->p[2] : NULL, j->p[3], j->batch, j->where);
+}
+static napi_value ctx_ct_square_relin(napi_env env, napi_callback_info info) {
+    static const char *usage = "ctSquareRelinPrepared(ct, ref | null, rlkPrep, baseLog, out)";
+    call k;
+    if (call_begin(env, info, 5, &k)) return NULL;
+    uint64_t *x, *r = NULL, *kk, *o, bl;
+    size_t nx, nr = 0, nk, no;
+    if (arr_arg(env, &k, 0, &x, &nx) || (!undef_arg(env, &k, 1) && arr_arg(env, &k, 1, &r, &nr)) ||
+        arr_arg(env, &k, 2, &kk, &nk) || num_arg(env, &k, 3, &bl) || arr_arg(env, &k, 4, &o, &no))
+        return bad_args(env, usage), NULL;
+    const size_t per = 2 * k.n;
+    if (nx % per || nk % per || no != nx)
+        return range_err(env, "ct [batch][2][n], rlk [level][2][n], out [batch][2][n]");
+    if (r && nr != per && nr != nx) return range_err(env, "ref must be one ciphertext [2][n] or the shape of ct");
+    job *j = job_new(&k, run_ct_square_relin, NULL);
+    j->p[0] = x; j->p[1] = r; j->p[2] = kk; j->p[3] = o;
+    j->v[0] = bl ? bl : 4; j->v[1] = nk / per; j->v[2] = r ? nr / per : 0; j->batch = nx / per;
+    napi_value keep[4] = {k.argv[0], k.argv[2], k.argv[4], k.argv[1]};  /* a null ref is not kept */
+    return job_go(env, &k, j, k.argv[4], keep, r ? 4 : 3);
+}
+
 /* blindRotate(acc, lweA, lweB, bsk, baseLog, level): k = 1, in place on acc
  * [batch][2][n]; lweA [batch][dim]; lweB [batch]; bsk [dim][2*level][2][n]
  * coefficient-form GGSWs, host buffers (BootstrapEngine::blind_rotate :547-577) */
@@ -1706,6 +1756,8 @@ static napi_value init(napi_env env, napi_value exports) {
         M("relinearize", ctx_relinearize),
         M("prepareRelinKey", ctx_prep_rlk),
         M("relinearizePrepared", ctx_relin_prepared),
+        M("ctSquare", ctx_ct_square),
+        M("ctSquareRelinPrepared", ctx_ct_square_relin),
         M("blindRotate", ctx_blind_rotate),
         M("preparePublicKey", ctx_pk_prep),
         M("prepareSecretKey", ctx_sk_prep),
