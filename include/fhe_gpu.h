@@ -490,6 +490,54 @@ int fhe_decrypt_batch(fhe_ctx *ctx, uint64_t t, const uint64_t *sk_prep, const u
 int fhe_add_plain_batch(fhe_ctx *ctx, uint64_t t, const uint64_t *ct, const uint64_t *values, int is_ntt,
                         uint64_t *out, size_t batch, int where);
 
+/* ---- threshold decryption (key_manager.cpp:479-636) ----
+ * A tally under a threshold key is opened by trustees: each computes a partial
+ * decryption with a Shamir share of the secret key, and `threshold` partials
+ * are combined and decoded.  Batched over ciphertexts [batch][2][n].
+ * fhe_shamir_shares_batch  generate_threshold_keys' evaluation (:511-526):
+ *   coeffs [threshold][n] (row 0 the master key, rows 1.. the random
+ *   polynomials) -> shares [total][n],
+ *   shares[i-1][j] = sum_k ((coeffs[k][j] mod q) (i^k mod q) mod q) mod q,
+ *   i = 1..total.  1 <= threshold <= total, else FHE_ERR_INVALID_ARG "Invalid
+ *   threshold parameters" (:484-486).
+ * fhe_key_share_prepare  shares [count][n] -> shares_prep [count][n], the
+ *   NTT-domain form partial decryption multiplies with.  Opaque, like sk_prep:
+ *   pass it back to the context that made it.
+ * fhe_partial_decrypt_batch  partial_decrypt (:584-601) of every ciphertext
+ *   with every given share: partials [nshares][batch][n], partials[s][b] =
+ *   c1_b * share_s in the ring -- the words of fhe_polymul_batch(c1, share).
+ *   Only c1 is read.  nshares >= 1 and batch >= 1, else FHE_ERR_INVALID_ARG;
+ *   partials must not overlap ct.
+ * fhe_lagrange_coefficients  lagrange_coefficient (:548-582) on the host (no
+ *   GPU): lambdas[i], i < used, for share_ids[i] over ALL `count` ids --
+ *   numerator prod_{j != i} j mod q, denominator prod_{j != i} (j - i) mod q
+ *   with the reference's signed subtraction, inverted by
+ *   NTTProcessor::mod_inverse.  (combine_partial_decryptions interpolates over
+ *   every supplied index and sums only the first `threshold` partials.)
+ *   count == 0, used == 0 or used > count: FHE_ERR_INVALID_ARG; a zero id or
+ *   two equal ids: FHE_ERR_INVALID_ARG "share ids must be distinct and
+ *   non-zero" (the reference's denominator is 0 there).
+ * fhe_combine_partials_batch  combine_partial_decryptions (:623-635) and the
+ *   decryption it serves: partials [count][batch][n], one [batch][n] block per
+ *   trustee; lambdas a HOST array of `count` words in both residences, copied
+ *   before the call returns.  phase = c0 - sum_i partials[i] lambdas[i]: the
+ *   words of fhe_poly_mul_scalar_batch and fhe_poly_add_batch per partial,
+ *   then fhe_poly_sub_batch(c0, .).  values [batch][n], phase [batch][n] and
+ *   max_noise [batch] (each nullable, at least one given) are what
+ *   fhe_decrypt_batch gives for that phase; t == 0 selects 4.  Only c0 is
+ *   read.  count == 0: FHE_ERR_INVALID_ARG.
+ * On a multi-device context the batch is split into contiguous ranges; every
+ * device takes all shares / all partials of its range. */
+int fhe_shamir_shares_batch(fhe_ctx *ctx, const uint64_t *coeffs, uint32_t threshold, uint32_t total,
+                            uint64_t *shares, int where);
+int fhe_key_share_prepare(fhe_ctx *ctx, const uint64_t *shares, uint64_t *shares_prep, size_t count, int where);
+int fhe_partial_decrypt_batch(fhe_ctx *ctx, const uint64_t *shares_prep, size_t nshares, const uint64_t *ct,
+                              uint64_t *partials, size_t batch, int where);
+int fhe_lagrange_coefficients(uint64_t q, const uint32_t *share_ids, size_t count, size_t used, uint64_t *lambdas);
+int fhe_combine_partials_batch(fhe_ctx *ctx, uint64_t t, const uint64_t *ct, const uint64_t *partials,
+                               const uint64_t *lambdas, size_t count, uint64_t *values, uint64_t *phase,
+                               uint64_t *max_noise, size_t batch, int where);
+
 /* ---- BootstrapEngine::bootstrap_with_test_poly (bootstrap_engine.cpp:684-708)
  * For each LWE ciphertext c (lwe_a [batch][lwe_dim], lwe_b [batch] mod
  * lwe_q): acc = (0, .., 0, test_poly), blind_rotate (as

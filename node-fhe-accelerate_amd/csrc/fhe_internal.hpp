@@ -204,6 +204,33 @@ inline void scalar_entry(uint64_t raw, uint64_t q, uint64_t e[2]) {
     e[0] = (q >> 63) ? (uint64_t)((s << 64) % q) : (uint64_t)s;
     e[1] = (q >> 63) ? 0 : (uint64_t)((s << 64) / q);
 }
+// Threshold decryption (threshold.hip; key_manager.cpp:479-636).
+// launch_partial_dec: partials[s][b] = inv(fwd(c1_b) (.) shares_prep[s]) for
+// ct [batch][2][n] (c1 read in place) and prepared rows [nshares][n] (NTT x R);
+// block s of the output starts at partials + s share_stride.  The fused family
+// only (n <= 16384, q < 2^62).
+hipError_t launch_partial_dec(const Plan &p, const uint64_t *shares_prep, size_t nshares, const uint64_t *ct,
+                              uint64_t *partials, size_t share_stride, size_t batch);
+// launch_combine_partials: phase = c0 - sum_i partials[i] lambda_i, decoded as
+// k_decode does; block i of the partials starts at partials + i share_stride.
+// Up to kCombineInlineLambdas partials take `lambdas`, the raw HOST words
+// (they travel as kernel arguments, lam unused); more take lam, a device table
+// of `count` scalar_entry pairs (launch_scalar_table).  values, phase and
+// max_noise are each nullable (max_noise is zeroed by the launch).  Any n >=
+// 2 that is a power of two, any odd q.
+constexpr int kCombineInlineLambdas = 16;
+hipError_t launch_combine_partials(const ModConsts &m, uint64_t t, const uint64_t *ct, const uint64_t *partials,
+                                   size_t share_stride, const uint64_t *lambdas, const void *lam, size_t count,
+                                   uint64_t *values, uint64_t *phase, uint64_t *max_noise, uint32_t n, size_t batch,
+                                   hipStream_t s);
+// launch_scalar_table: `count` HOST scalars to a device table of scalar_entry
+// pairs.  The entries travel as kernel arguments, so the host array is free
+// when the call returns and nothing is synchronised.
+hipError_t launch_scalar_table(uint64_t q, const uint64_t *raw, size_t count, void *tab, hipStream_t s);
+// launch_shamir_shares: shares[i - 1] = sum_k coeffs[k] i^k, i = 1..total;
+// pts is a device table of `total` scalar_entry pairs of the points 1..total.
+hipError_t launch_shamir_shares(const ModConsts &m, const uint64_t *coeffs, uint32_t threshold, uint32_t total,
+                                const void *pts, uint64_t *shares, size_t n, hipStream_t s);
 // Ciphertext inner product with public plaintext polynomials (dot_plain.hip):
 // cts [groups][count][2][n], pts [groups][count][n], or with ptr_table device
 // arrays of `count` pointers each (groups == 1); slices as launch_ct_dot, rows

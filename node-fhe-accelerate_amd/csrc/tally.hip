@@ -28,30 +28,12 @@
 // reduction at the end,
 // hi 2^64 + lo = wmont(hi, 2^128 mod q) + lo (mod q), is exact for any odd
 // q < 2^64 and any count < 2^64 (as lwe.hip's split key-switch sum).
-#include "fhe_internal.hpp"
+#include "tally_ops.hpp"
 
 namespace FHE_NS {
 
 static constexpr int kBlock = 256;
 static constexpr int kUnroll = 8;
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-struct TallyAcc {
-    uint64_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
-    __device__ __forceinline__ void add(u64x2 v) {
-        lo0 += v.x;
-        hi0 += lo0 < v.x;
-        lo1 += v.y;
-        hi1 += lo1 < v.y;
-    }
-};
-
-__device__ __forceinline__ uint64_t fold128(uint64_t hi, uint64_t lo, const ModConsts &m) {
-    const uint64_t l = mod64_slow(lo, m.q, m.mu);
-    if (hi == 0) return l;
-    const uint64_t h = wmont(mod64_slow(hi, m.q, m.mu), m.r2, m.q, m.qinv);  // hi 2^64 mod q
-    return wadd(h, l, m.q);
-}
 
 // PTR = false: src is [groups][count][words] u64.  PTR = true: src is a table
 // of `count` pointers to `words` u64 each (gridDim.z == 1).
@@ -121,16 +103,10 @@ hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, ui
 //              the canonical product with the carry bit, in place of
 //              mul_scalar's 128-step shift-subtract.
 // Products are canonical; they are summed and folded as k_ct_sum's words.  A
-// prior `out` (accumulate) is one more unscaled term.  The choice between the
-// two products is made once per kernel (WIDE), outside every loop: as a branch
-// per word the compiler ran the wmont product unconditionally beside the
-// Shoup one.
-template <bool WIDE>
-__device__ __forceinline__ uint64_t scaled1(uint64_t x, u64x2 s, const ModConsts &m) {
-    if constexpr (WIDE) return wmont(x >= m.q ? x - m.q : x, s.x, m.q, m.qinv);
-    else return shoup64(x, s.x, s.y, m.q);
-}
-
+// prior `out` (accumulate) is one more unscaled term.  The product is scaled1
+// (tally_ops.hpp); the choice between its two forms is made once per kernel
+// (WIDE), outside every loop: as a branch per word the compiler ran the wmont
+// product unconditionally beside the Shoup one.
 __global__ void __launch_bounds__(kBlock)
 k_scalar_prep(const uint64_t *__restrict__ raw, u64x2 *__restrict__ tab, size_t total, ModConsts m) {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;

@@ -157,6 +157,12 @@ SIGNATURES = [
     ("fhe_decrypt_batch", C.c_int,
      [vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_add_plain_batch", C.c_int, [vp, C.c_uint64, vp, vp, C.c_int, vp, C.c_size_t, C.c_int]),
+    ("fhe_shamir_shares_batch", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_int]),
+    ("fhe_key_share_prepare", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_partial_decrypt_batch", C.c_int, [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_lagrange_coefficients", C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.c_size_t, C.c_size_t, u64p]),
+    ("fhe_combine_partials_batch", C.c_int,
+     [vp, C.c_uint64, vp, vp, u64p, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_bootstrap_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_uint32,
       C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
@@ -835,6 +841,81 @@ class PublicKey:
         _check(lib().fhe_public_key_prepare(ring._h, bi.ptr, bo.ptr, w))
 
 
+def _placed_like(x, like):
+    """x on the side of `like` (host array or device tensor)."""
+    if _is_tensor(like) and not _is_tensor(x):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).to(like.device)
+    if _is_tensor(x) and not _is_tensor(like):
+        return x.cpu().numpy().view(np.uint64)
+    return x
+
+
+def lagrange_coefficients(q: int, share_ids, used=None):
+    """KeyManager::lagrange_coefficient (key_manager.cpp:548-582) at 0 for the
+    first ``used`` of ``share_ids`` (default: all), interpolating over every
+    id given (fhe_lagrange_coefficients; needs no GPU)."""
+    ids = [int(i) for i in share_ids]
+    used = len(ids) if used is None else int(used)
+    if any(not 0 <= i < 1 << 32 for i in ids):
+        raise FHEError(-9, "share ids must be 32-bit unsigned integers")
+    arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+    out = (C.c_uint64 * max(used, 1))()
+    _check(lib().fhe_lagrange_coefficients(int(q), arr, len(ids), max(used, 0), out))
+    return [int(out[i]) for i in range(used)]
+
+
+def shamir_shares(ring: "NTTProcessor", coeffs, total_shares: int, out=None):
+    """The Shamir evaluation of generate_threshold_keys (key_manager.cpp:
+    511-526): coeffs [threshold, n] -> shares [total_shares, n] at the points
+    1..total_shares (fhe_shamir_shares_batch)."""
+    coeffs = _as_u64(coeffs)
+    if len(coeffs.shape) != 2 or coeffs.shape[1] != ring.degree:
+        raise FHEError(-9, "coeffs must have shape [threshold, n]")
+    total_shares = int(total_shares)
+    if out is None:
+        out = _empty(coeffs, (max(total_shares, 0), ring.degree))
+    bc, bo = _Buf(coeffs), _Buf(out, True)
+    if bo.count != total_shares * ring.degree:
+        raise FHEError(-9, "out must have shape [total_shares, n]")
+    w = _where(bc, bo)
+    ring._bind_stream(w)
+    _check(lib().fhe_shamir_shares_batch(ring._h, bc.ptr, int(coeffs.shape[0]), total_shares, bo.ptr, w))
+    return out
+
+
+class KeyShare:
+    """SecretKeyShare (key_manager.h): the share's id (its evaluation point)
+    and polynomial [n]; the NTT-domain form partial decryption multiplies with
+    is prepared on first use (fhe_key_share_prepare) and kept."""
+
+    def __init__(self, ring: "PolynomialRing", share_id: int, poly):
+        s = _as_u64(poly)
+        if tuple(s.shape) != (ring.degree,):
+            raise FHEError(-9, "a key share must have shape [n]")
+        self.ring, self.share_id, self.poly = ring, int(share_id), s
+        self._prep = None
+
+    @property
+    def prep(self):
+        if self._prep is None:
+            out = _like(self.poly)
+            bi, bo = _Buf(self.poly), _Buf(out, True)
+            w = _where(bi, bo)
+            self.ring._bind_stream(w)
+            _check(lib().fhe_key_share_prepare(self.ring._h, bi.ptr, bo.ptr, 1, w))
+            self._prep = out
+        return self._prep
+
+
+class ThresholdKeys:
+    """ThresholdKeys (key_manager.h): the trustees' shares, the master secret
+    key they interpolate to (for dealers and tests), and the parameters."""
+
+    def __init__(self, shares, secret_key, threshold: int, total_shares: int):
+        self.shares, self.secret_key = list(shares), secret_key
+        self.threshold, self.total_shares = int(threshold), int(total_shares)
+
+
 SAMPLE_UNIFORM, SAMPLE_TERNARY, SAMPLE_GAUSSIAN, SAMPLE_BINARY, SAMPLE_RAW = range(5)
 
 
@@ -905,6 +986,24 @@ class KeyGenerator:
         _check(lib().fhe_eval_key_generate(r._h, bs.ptr, base_log, level, _seed_arr(self.seed), stream,
                                            self.noise_std, bo.ptr, w))
         return out
+
+    def threshold_keys(self, threshold: int, total_shares: int, stream: int, device_out: bool = False):
+        """generate_threshold_keys (:479-546): a ternary master key from
+        ``stream``, the random sharing polynomial j (1 <= j < threshold) from
+        ``stream + j`` (uniform, n draws each), and the shares at the points
+        1..total_shares (fhe_shamir_shares_batch) -> ThresholdKeys."""
+        r = self.ring
+        threshold, total_shares = int(threshold), int(total_shares)
+        if threshold < 1 or threshold > total_shares:
+            raise FHEError(-9, "Invalid threshold parameters")
+        master = self.secret_key(stream, device_out=device_out)
+        coeffs = _empty(master, (threshold, r.degree))
+        coeffs[0] = master
+        for j in range(1, threshold):
+            sample(r, SAMPLE_UNIFORM, self.seed, stream + j, r.degree, out=coeffs[j])
+        shares = shamir_shares(r, coeffs, total_shares)
+        return ThresholdKeys([KeyShare(r, i + 1, shares[i]) for i in range(total_shares)], SecretKey(r, master),
+                             threshold, total_shares)
 
     def ggsw(self, values, sk, k: int, base_log: int, level: int, stream: int, out=None):
         """encrypt_ggsw (bootstrap_engine.cpp:268-306) of int64 values ->
@@ -1069,6 +1168,81 @@ class EncryptionEngine:
         r._bind_stream(w)
         _check(lib().fhe_decrypt_batch(r._h, self.t, bs.ptr, bc.ptr, comps, int(bool(is_ntt)), bv.ptr,
                                        bp.ptr if bp else None, bm.ptr, nb, w))
+        if _is_tensor(mx):
+            torch.cuda.current_stream(mx.device).synchronize()
+        return DecryptionResult(vals, mx, r.modulus, ph)
+
+    def partial_decrypt(self, ct, shares, out=None):
+        """KeyManager::partial_decrypt (key_manager.cpp:584-601) of every
+        ciphertext [..., 2, n] with every given KeyShare, in one launch:
+        c1 * share in the ring -> [len(shares), ..., n], or [..., n] for a
+        single KeyShare."""
+        r = self.ring
+        ct = _as_u64(ct)
+        single = isinstance(shares, KeyShare)
+        lst = [shares] if single else list(shares)
+        if not lst:
+            raise FHEError(-9, "at least one key share is needed")
+        nb = _lead(ct, (2, r.degree))
+        lead = tuple(ct.shape[:-2])
+        preps = [_placed_like(k.prep, ct) for k in lst]
+        prep = preps[0] if len(preps) == 1 else (torch.stack(preps) if _is_tensor(ct) else np.stack(preps))
+        shape = (() if single else (len(lst),)) + lead + (r.degree,)
+        if out is None:
+            out = _empty(ct, shape)
+        bs, bc, bo = _Buf(prep), _Buf(ct), _Buf(out, True)
+        if bo.count != len(lst) * nb * r.degree:
+            raise FHEError(-9, f"out must have shape {list(shape)}")
+        w = _where(bs, bc, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_partial_decrypt_batch(r._h, bs.ptr, len(lst), bc.ptr, bo.ptr, nb, w))
+        return out
+
+    def combine_partial_decryptions(self, ct, partials, share_ids, threshold=None, with_phase: bool = False):
+        """KeyManager::combine_partial_decryptions (key_manager.cpp:604-636)
+        and the decryption it opens: partials [count, ..., n] (an array, or a
+        list of [..., n] blocks, one per trustee) for the ciphertexts
+        [..., 2, n], share_ids their ids.  As the reference, the Lagrange
+        coefficients interpolate over every id given and the first
+        ``threshold`` partials (default: all) are summed; phase = c0 - sum,
+        decoded like decrypt -> DecryptionResult (with max_noise)."""
+        r = self.ring
+        ct = _as_u64(ct)
+        ids = [int(i) for i in share_ids]
+        threshold = len(ids) if threshold is None else int(threshold)
+        if isinstance(partials, (list, tuple)):
+            blocks = [_placed_like(_as_u64(p), ct) for p in partials]
+            partials = (torch.stack(blocks) if _is_tensor(ct) else np.stack(blocks)) if blocks else None
+        else:
+            partials = _placed_like(_as_u64(partials), ct)
+        count = 0 if partials is None else int(partials.shape[0])
+        if count != len(ids):
+            raise FHEError(-9, "one share id per partial decryption is needed")
+        if count < threshold or threshold < 1:
+            raise FHEError(-9, "Not enough partial decryptions")
+        return self.combine_partials(ct, partials[:threshold], lagrange_coefficients(r.modulus, ids, threshold), with_phase)
+
+    def combine_partials(self, ct, partials, lambdas, with_phase: bool = False):
+        """phase = c0 - sum_i partials[i] lambdas[i] for ct [..., 2, n] and
+        partials [count, ..., n], decoded like decrypt (fhe_combine_partials_batch)
+        -> DecryptionResult.  lambdas: count integers (any u64, read mod q)."""
+        r = self.ring
+        ct = _as_u64(ct)
+        partials = _placed_like(_as_u64(partials), ct)
+        lam = [int(x) for x in lambdas]
+        nb = _lead(ct, (2, r.degree))
+        lead = tuple(ct.shape[:-2])
+        if not lam or tuple(partials.shape) != (len(lam),) + lead + (r.degree,):
+            raise FHEError(-9, f"partials must have shape {[len(lam)] + list(lead) + [r.degree]}, one block per lambda")
+        vals = _empty(ct, lead + (r.degree,))
+        mx = _empty(ct, lead if lead else (1,))
+        ph = _empty(ct, lead + (r.degree,)) if with_phase else None
+        bc, bq, bv, bm = _Buf(ct), _Buf(partials), _Buf(vals, True), _Buf(mx, True)
+        bp = _Buf(ph, True) if ph is not None else None
+        w = _where(bc, bq, bv, bm, bp)
+        r._bind_stream(w)
+        _check(lib().fhe_combine_partials_batch(r._h, self.t, bc.ptr, bq.ptr, (C.c_uint64 * len(lam))(*lam), len(lam),
+                                                bv.ptr, bp.ptr if bp else None, bm.ptr, nb, w))
         if _is_tensor(mx):
             torch.cuda.current_stream(mx.device).synchronize()
         return DecryptionResult(vals, mx, r.modulus, ph)

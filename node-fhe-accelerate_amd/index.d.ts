@@ -269,6 +269,17 @@ export interface FHEAnomalyEngine extends FHEPublicWeightEngine {
   computeAnomalyScore(ballot: Ciphertext, expected: Ciphertext, ek: EvaluationKey): Promise<Ciphertext>;
 }
 
+/** Batched threshold decryption: a trustee's partial decryptions of many tallies
+ * in one launch (fhe_partial_decrypt_batch, the share's transform prepared once),
+ * and their combination, decoding and noise measurement in one launch
+ * (fhe_combine_partials_batch).  partials[i] is trustee i's list, index-aligned
+ * with cts; the results equal partialDecrypt / combinePartialDecryptions per
+ * ciphertext, with remainingNoiseBudget taken from the measured noise. */
+export interface FHEThresholdEngine extends FHEAnomalyEngine {
+  partialDecryptBatch(cts: Ciphertext[], share: ThresholdKeys['shares'][0]): Promise<PartialDecryption[]>;
+  combinePartialDecryptionsBatch(cts: Ciphertext[], partials: PartialDecryption[][], t: number): Promise<DecryptionResult[]>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -331,6 +342,8 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   tallyScalarWeightedVotes(ballots: Ciphertext[], weights: bigint[], progress?: ProgressCallback): Promise<Ciphertext>;
   dotPlain(cts: Ciphertext[], pts: Plaintext[], progress?: ProgressCallback): Promise<Ciphertext>;
   computeAnomalyScore(ballot: Ciphertext, expected: Ciphertext, ek: EvaluationKey): Promise<Ciphertext>;
+  partialDecryptBatch(cts: Ciphertext[], share: ThresholdKeys['shares'][0]): Promise<PartialDecryption[]>;
+  combinePartialDecryptionsBatch(cts: Ciphertext[], partials: PartialDecryption[][], t: number): Promise<DecryptionResult[]>;
   /** The device buffer behind a handle (this backend's extension). */
   deviceBuffer(handle: unknown): DeviceBuffer | undefined;
 }
@@ -417,6 +430,23 @@ export declare class NttContext {
    * (fhe_ct_square_relin_batch); coefficient form. */
   ctSquareRelinPrepared(ct: Words, ref: Words | null, rlkPrep: Words, baseLog: number, out: Words): Words;
   ctSquareRelinPreparedAsync(ct: Words, ref: Words | null, rlkPrep: Words, baseLog: number, out: Words): Promise<Words>;
+  /** shares [total][n] of generate_threshold_keys at the points 1..total from coeffs
+   * [threshold][n] (fhe_shamir_shares_batch). */
+  shamirShares(coeffs: Words, total: number, out: Words): Words;
+  shamirSharesAsync(coeffs: Words, total: number, out: Words): Promise<Words>;
+  /** shares [count][n] -> their NTT-domain form for partialDecryptPrepared (fhe_key_share_prepare). */
+  prepareKeyShares(shares: Words, out: Words): Words;
+  prepareKeySharesAsync(shares: Words, out: Words): Promise<Words>;
+  /** out [nshares][batch][n] = c1 * share for ct [batch][2][n] (fhe_partial_decrypt_batch). */
+  partialDecryptPrepared(sharesPrep: Words, ct: Words, out: Words): Words;
+  partialDecryptPreparedAsync(sharesPrep: Words, ct: Words, out: Words): Promise<Words>;
+  /** phase = c0 - sum_i partials[i] lambdas[i] of ct [batch][2][n], partials [count][batch][n],
+   * decoded into values [batch][n] with maxNoise [batch] (fhe_combine_partials_batch);
+   * lambdas is always a host array. */
+  combinePartials(t: bigint, ct: Words, partials: Words, lambdas: BigUint64Array, values: Words, maxNoise: Words,
+    phase?: Words): Words;
+  combinePartialsAsync(t: bigint, ct: Words, partials: Words, lambdas: BigUint64Array, values: Words, maxNoise: Words,
+    phase?: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;
@@ -463,6 +493,9 @@ export declare class PolynomialEngine {
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out?: Words): Words;
   ctMultiply(ct1: Words, ct2: Words, opts?: { isNtt?: boolean }, out?: Words): Words;
   ctSquare(ct: Words, ref?: Words | null, opts?: { isNtt?: boolean }, out?: Words): Words;
+  partialDecrypt(ct: Words, shares: Words, out?: Words): Words;
+  combinePartials(ct: Words, partials: Words, lambdas: ArrayLike<bigint>, t?: bigint):
+    { values: BigUint64Array; maxNoise: BigUint64Array; phase: BigUint64Array };
   relinearize(ct3: Words, rlk: Words, baseLog?: number, out?: Words): Words;
   multiplyRelin(ct1: Words, ct2: Words, rlk: Words, baseLog?: number): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

@@ -373,81 +373,151 @@ function makeEngineClass(native) {
 
     /** KeyManager::generate_threshold_keys (key_manager.cpp:479-560): Shamir
      *  shares s_i = sum_j coeff_j i^j of a fresh ternary master key
-     *  (coefficients j >= 1 uniform), computed on the device. */
+     *  (coefficients j >= 1 uniform), all shares in one launch. */
     async generateThresholdKeys(config) {
       this._check();
       return guard(async () => {
         const t = config && config.threshold | 0, total = config && config.totalShares | 0;
         if (t <= 0 || t > total) throw new FHEError('Invalid threshold parameters', FHEErrorCode.INVALID_PARAMETERS);
+        const n = this._n;
         const master = await this.generateSecretKey();
-        const ms = state.get(master);
-        const coeffs = [ms.buf];
+        const coeffs = this._buf(t * n);
+        coeffs.view(0, n).copyFrom(state.get(master).buf);
         for (let j = 1; j < t; j++) {
-          const c = this._buf(this._n);
-          await this._ctx.sampleAsync(SAMPLE.UNIFORM, this._seed, this._streams(1), 0, c);
-          coeffs.push(c);
+          await this._ctx.sampleAsync(SAMPLE.UNIFORM, this._seed, this._streams(1), 0, coeffs.view(j * n, n));
         }
+        const all = this._buf(total * n);
+        await this._ctx.shamirSharesAsync(coeffs, total, all);
+        coeffs.free();
+        const words = all.download();
         const shares = [];
         for (let i = 1; i <= total; i++) {
-          const acc = this._buf(this._n), term = this._buf(this._n);
-          let pw = 1n;
-          for (let j = 0; j < t; j++) {
-            await this._ctx.mulScalarAsync(coeffs[j], pw, j === 0 ? acc : term);
-            if (j > 0) await this._ctx.addAsync(acc, term, acc);
-            pw = (pw * BigInt(i)) % this._q;
-          }
-          term.free();
-          const commitment = new Uint8Array(crypto.createHash('sha256').update(Buffer.from(acc.download().buffer)).digest());
-          const h = Object.freeze({ shareId: i, handle: acc.handle, commitment, keyId: master.keyId });
-          state.set(h, { engine: this, buf: acc });
+          const buf = all.view((i - 1) * n, n);
+          const bytes = Buffer.from(words.buffer, words.byteOffset + (i - 1) * n * 8, n * 8);
+          const commitment = new Uint8Array(crypto.createHash('sha256').update(bytes).digest());
+          const h = Object.freeze({ shareId: i, handle: buf.handle, commitment, keyId: master.keyId });
+          state.set(h, { engine: this, buf });
           shares.push(h);
         }
         const publicKey = await this.generatePublicKey(master);
         return { shares, publicKey, threshold: t, totalShares: total };
       });
     }
+    /** the share's state, its NTT-domain form prepared on first use and kept */
+    async _share(share) {
+      const s = share && state.get(share);
+      if (!s || s.engine !== this || share.shareId === undefined) {
+        throw new FHEError('not a key share of this engine', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (!s.prep) {
+        const prep = this._buf(this._n);
+        await this._ctx.prepareKeySharesAsync(s.buf, prep);
+        s.prep = prep;
+      }
+      return s;
+    }
+    /** partial decryptions of cts with one share: one launch over the batch */
+    async _partials(cts, share) {
+      const n = this._n, B = cts.length;
+      const cs = cts.map((ct) => this._rlwe(ct));
+      const s = await this._share(share);
+      for (const ct of cts) {
+        if (share.keyId !== ct.keyId) throw new FHEError('Key share does not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      }
+      let all = cs[0].buf;
+      if (B > 1 || cs[0].comps !== 2) {
+        all = this._buf(B * 2 * n);
+        cs.forEach((c, i) => all.view(i * 2 * n, 2 * n).copyFrom(c.comps === 2 ? c.buf : c.buf.view(0, 2 * n)));
+      }
+      const p = this._buf(B * n);
+      await this._ctx.partialDecryptPreparedAsync(s.prep, all, p);
+      const w = p.download();
+      if (all !== cs[0].buf) all.free();
+      p.free();
+      return cts.map((_, i) => ({ shareId: share.shareId, partialResult: toBigIntArray(w.subarray(i * n, (i + 1) * n), n) }));
+    }
     /** KeyManager::partial_decrypt (:584-601): c1 (*) share */
     async partialDecrypt(ct, share) {
       this._check();
+      return guard(async () => (await this._partials([ct], share))[0]);
+    }
+    /** partialDecrypt of every ciphertext with one share, one launch */
+    async partialDecryptBatch(cts, share) {
+      this._check();
       return guard(async () => {
-        const c = this._rlwe(ct);
-        const s = share && state.get(share);
-        if (!s || s.engine !== this) throw new FHEError('not a key share of this engine', FHEErrorCode.INVALID_PARAMETERS);
-        if (share.keyId !== ct.keyId) throw new FHEError('Key share does not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
-        const p = this._buf(this._n);
-        await this._ctx.polymulAsync(c.buf.view(this._n, this._n), s.buf, p);
-        const w = p.download();
-        return { shareId: share.shareId, partialResult: toBigIntArray(w, this._n) };
+        if (!Array.isArray(cts)) throw new FHEError('expected an array of ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+        return cts.length ? this._partials(cts, share) : [];
       });
+    }
+    /** lagrange_coefficient (:566-582) for the first t of the partials' ids, over all of them */
+    _lambdas(ids, t) {
+      const q = this._q, out = new BigUint64Array(t);
+      for (let i = 0; i < t; i++) {
+        let num = 1n, den = 1n;
+        for (const j of ids) {
+          if (j === ids[i]) continue;
+          num = (num * j) % q;
+          den = (den * (((j - ids[i]) % q + q) % q)) % q;
+        }
+        out[i] = (num * modPow(den, q - 2n, q)) % q;
+      }
+      return out;
+    }
+    /** combine (:604-632) + c0 - sum + decode of cts, partials[i][b] trustee i's
+     *  partial of ciphertext b: one upload, one launch, no host decode */
+    async _combine(cts, partials, t) {
+      const n = this._n, B = cts.length;
+      const cs = cts.map((ct) => this._rlwe(ct));
+      if (!Array.isArray(partials) || partials.length < t || t < 1) {
+        throw new FHEError(`Need ${t} partials, got ${partials ? partials.length : 0}`, FHEErrorCode.THRESHOLD_NOT_MET);
+      }
+      for (const list of partials) {
+        if (!Array.isArray(list) || list.length !== B) {
+          throw new FHEError('every trustee needs one partial decryption per ciphertext', FHEErrorCode.INVALID_PARAMETERS);
+        }
+        if (list.some((p) => p.shareId !== list[0].shareId)) {
+          throw new FHEError('the partial decryptions of one trustee carry one share id', FHEErrorCode.INVALID_PARAMETERS);
+        }
+      }
+      const lam = this._lambdas(partials.map((list) => BigInt(list[0].shareId)), t);
+      const host = new BigUint64Array(t * B * n);
+      for (let i = 0; i < t; i++) {
+        for (let b = 0; b < B; b++) {
+          const r = partials[i][b].partialResult, o = (i * B + b) * n;
+          for (let k = 0; k < n; k++) host[o + k] = u64(r[k]);
+        }
+      }
+      const pb = this._upload(host);
+      let all = cs[0].buf;
+      if (B > 1 || cs[0].comps !== 2) {
+        all = this._buf(B * 2 * n);
+        cs.forEach((c, i) => all.view(i * 2 * n, 2 * n).copyFrom(c.comps === 2 ? c.buf : c.buf.view(0, 2 * n)));
+      }
+      const vals = this._buf(B * n), mx = this._buf(B);
+      await this._ctx.combinePartialsAsync(this._t, all, pb, lam, vals, mx);
+      const v = vals.download(), m = mx.download();
+      if (all !== cs[0].buf) all.free();
+      pb.free(); vals.free(); mx.free();
+      return cs.map((c, b) => ({ vals: v.slice(b * n, (b + 1) * n), maxNoise: m[b], packed: c.packed }));
     }
     /** combine_partial_decryptions (:604-632) with lagrange_coefficient
      *  (:566-582), then c0 - sum and decode (decode_packed :150-163) */
     async combinePartialDecryptions(ct, partials, t) {
       this._check();
       return guard(async () => {
-        const c = this._rlwe(ct);
-        if (!Array.isArray(partials) || partials.length < t) {
-          throw new FHEError(`Need ${t} partials, got ${partials ? partials.length : 0}`, FHEErrorCode.THRESHOLD_NOT_MET);
-        }
-        const q = this._q, idx = partials.map((p) => BigInt(p.shareId));
-        const acc = this._buf(this._n), term = this._buf(this._n), pb = this._buf(this._n);
-        for (let i = 0; i < partials.length && i < t; i++) {
-          let num = 1n, den = 1n;
-          for (const j of idx) {
-            if (j === idx[i]) continue;
-            num = (num * j) % q;
-            den = (den * (((j - idx[i]) % q + q) % q)) % q;
-          }
-          const lambda = (num * modPow(den, q - 2n, q)) % q;
-          pb.upload(BigUint64Array.from(partials[i].partialResult.map((x) => u64(x))));
-          await this._ctx.mulScalarAsync(pb, lambda, i === 0 ? acc : term);
-          if (i > 0) await this._ctx.addAsync(acc, term, acc);
-        }
-        await this._ctx.subAsync(c.buf.view(0, this._n), acc, acc);
-        const phase = acc.download();
-        const vals = new BigUint64Array(this._n);
-        for (let i = 0; i < this._n; i++) vals[i] = ((phase[i] * this._tEff + q / 2n) / q) % this._tEff;
-        return this._decryptionResult(vals, null, c.packed);
+        const lists = Array.isArray(partials) ? partials.map((p) => [p]) : partials;
+        const r = (await this._combine([ct], lists, t))[0];
+        return this._decryptionResult(r.vals, null, r.packed);
+      });
+    }
+    /** combinePartialDecryptions of every ciphertext, partials[i] trustee i's
+     *  list index-aligned with cts: one launch; the budget is the measured one */
+    async combinePartialDecryptionsBatch(cts, partials, t) {
+      this._check();
+      return guard(async () => {
+        if (!Array.isArray(cts)) throw new FHEError('expected an array of ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+        if (!cts.length) return [];
+        return (await this._combine(cts, partials, t)).map((r) => this._decryptionResult(r.vals, r.maxNoise, r.packed));
       });
     }
 

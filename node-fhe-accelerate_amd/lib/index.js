@@ -48,6 +48,20 @@ class PolynomialEngine {
   ctSquare(ct, ref = null, { isNtt = false } = {}, out = new BigUint64Array(ct.length / 2 * 3)) {
     return this.ctx.ctSquare(ct, ref, out, isNtt ? 1 : 0);
   }
+  /** KeyManager::partial_decrypt of every ciphertext [batch][2][n] with every
+   *  share [nshares][n] (coefficient form; prepared here): [nshares][batch][n] */
+  partialDecrypt(ct, shares, out = new BigUint64Array(shares.length / this.degree * (ct.length / 2))) {
+    return this.ctx.partialDecryptPrepared(this.ctx.prepareKeyShares(shares, new BigUint64Array(shares.length)), ct, out);
+  }
+  /** KeyManager::combine_partial_decryptions and the decryption it opens:
+   *  partials [count][batch][n], lambdas [count] -> { values [batch][n],
+   *  maxNoise [batch], phase [batch][n] } */
+  combinePartials(ct, partials, lambdas, t = 0n) {
+    const words = ct.length / 2, batch = words / this.degree;
+    const values = new BigUint64Array(words), maxNoise = new BigUint64Array(batch), phase = new BigUint64Array(words);
+    this.ctx.combinePartials(BigInt(t), ct, partials, BigUint64Array.from(lambdas, (x) => BigInt(x)), values, maxNoise, phase);
+    return { values, maxNoise, phase };
+  }
   /** EncryptionEngine::relinearize: ct3 [batch][3][n], rlk [level][2][n] (a_l, b_l) */
   relinearize(ct3, rlk, baseLog = 4, out = new BigUint64Array(ct3.length / 3 * 2)) {
     return this.ctx.relinearize(ct3, rlk, baseLog, out);

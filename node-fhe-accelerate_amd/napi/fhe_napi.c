@@ -1419,6 +1419,90 @@ static napi_value ctx_decrypt(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[5], k.argv + 1, ph ? 7 : 6);
 }
 
+/* ---- threshold decryption (key_manager.cpp:479-636) ----
+ * shamirShares(coeffs [threshold][n], total, out [total][n]): the shares of
+ * generate_threshold_keys at the points 1..total (:511-526) */
+static int run_shamir(job *j) {
+    return fhe_shamir_shares_batch(j->c, j->p[0], (uint32_t)j->v[0], (uint32_t)j->v[1], j->p[1], j->where);
+}
+static napi_value ctx_shamir(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 3, &k)) return NULL;
+    uint64_t *cf, *o, total;
+    size_t ncf, no;
+    if (arr_arg(env, &k, 0, &cf, &ncf) || num_arg(env, &k, 1, &total) || arr_arg(env, &k, 2, &o, &no) || ncf % k.n ||
+        total > 0xffffffffull || no != total * k.n)
+        return bad_args(env, "shamirShares(coeffs [threshold*n], total, out [total*n])"), NULL;
+    job *j = job_new(&k, run_shamir, NULL);
+    j->p[0] = cf; j->p[1] = o; j->v[0] = ncf / k.n; j->v[1] = total;
+    napi_value keep[2] = {k.argv[0], k.argv[2]};
+    return job_go(env, &k, j, k.argv[2], keep, 2);
+}
+/* prepareKeyShares(shares [count][n], out [count][n]): the NTT-domain form
+ * partialDecryptPrepared multiplies with */
+static int run_share_prep(job *j) { return fhe_key_share_prepare(j->c, j->p[0], j->p[1], j->batch, j->where); }
+static napi_value ctx_share_prep(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 2, &k)) return NULL;
+    uint64_t *a, *o;
+    size_t na, no;
+    if (arr_arg(env, &k, 0, &a, &na) || arr_arg(env, &k, 1, &o, &no) || na % k.n || no != na)
+        return bad_args(env, "prepareKeyShares(shares [count*n], out [count*n])"), NULL;
+    job *j = job_new(&k, run_share_prep, NULL);
+    j->p[0] = a; j->p[1] = o; j->batch = na / k.n;
+    return job_go(env, &k, j, k.argv[1], k.argv, 2);
+}
+/* partialDecryptPrepared(sharesPrep [nshares][n], ct [batch][2][n], out
+ * [nshares][batch][n]): partial_decrypt (:584-601) of every ciphertext with
+ * every share, one launch */
+static int run_partial_dec(job *j) {
+    return fhe_partial_decrypt_batch(j->c, j->p[0], (size_t)j->v[0], j->p[1], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_partial_dec(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 3, &k)) return NULL;
+    uint64_t *sp, *ct, *o;
+    size_t nsp, nct, no;
+    if (arr_arg(env, &k, 0, &sp, &nsp) || arr_arg(env, &k, 1, &ct, &nct) || arr_arg(env, &k, 2, &o, &no))
+        return bad_args(env, "partialDecryptPrepared(sharesPrep [nshares*n], ct [batch*2n], out [nshares*batch*n])"), NULL;
+    if (nsp % k.n || nct % (2 * k.n) || no != nsp / k.n * (nct / 2))
+        return range_err(env, "sharesPrep [nshares][n], ct [batch][2][n], out [nshares][batch][n]");
+    job *j = job_new(&k, run_partial_dec, NULL);
+    j->p[0] = sp; j->p[1] = ct; j->p[2] = o; j->v[0] = nsp / k.n; j->batch = nct / (2 * k.n);
+    return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+/* combinePartials(t, ct [batch][2][n], partials [count][batch][n], lambdas
+ * (host BigUint64Array, count words), values, maxNoise, phase?) -> values:
+ * combine_partial_decryptions (:604-636), phase = c0 - sum_i partials[i]
+ * lambdas[i], decoded and noise-measured as decrypt */
+static int run_combine(job *j) {
+    return fhe_combine_partials_batch(j->c, j->v[0], j->p[0], j->p[1], j->owned, (size_t)j->v[1], j->p[2], j->p[4],
+                                      j->p[3], j->batch, j->where);
+}
+static napi_value ctx_combine(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "combinePartials(t, ct [batch*2n], partials [count*batch*n], lambdas (BigUint64Array count), values, "
+        "maxNoise, phase?)";
+    call k;
+    if (call_begin(env, info, 7, &k)) return NULL;
+    uint64_t t, *ct, *pa, *lam, *v, *mx, *ph = NULL;
+    size_t nct, npa, nlam, nv, nmx, nph = 0;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &ct, &nct) || arr_arg(env, &k, 2, &pa, &npa) || k.argc < 4 ||
+        get_u64_array(env, k.argv[3], &lam, &nlam) || arr_arg(env, &k, 4, &v, &nv) || arr_arg(env, &k, 5, &mx, &nmx) ||
+        (!undef_arg(env, &k, 6) && arr_arg(env, &k, 6, &ph, &nph)) || nct % (2 * k.n))
+        return bad_args(env, usage), NULL;
+    const size_t batch = nct / (2 * k.n);
+    if (nlam == 0 || npa != nlam * batch * k.n || nv != batch * k.n || nmx != batch || (ph && nph != batch * k.n))
+        return range_err(env, "partials [count*batch*n], values [batch*n], maxNoise [batch], phase [batch*n]");
+    job *j = job_new(&k, run_combine, NULL);
+    j->owned = (uint64_t *)malloc(nlam * 8);
+    memcpy(j->owned, lam, nlam * 8);
+    j->p[0] = ct; j->p[1] = pa; j->p[2] = v; j->p[3] = mx; j->p[4] = ph;
+    j->v[0] = t; j->v[1] = nlam; j->batch = batch;
+    napi_value keep[5] = {k.argv[1], k.argv[2], k.argv[4], k.argv[5], k.argv[6]};
+    return job_go(env, &k, j, k.argv[4], keep, ph ? 5 : 4);
+}
+
 /* addPlain(t, ct, values, isNtt, out): EncryptionEngine::add_plain (:638-665) */
 static int run_add_plain(job *j) {
     return fhe_add_plain_batch(j->c, j->v[0], j->p[0], j->p[1], (int)j->v[1], j->p[2], j->batch, j->where);
@@ -1765,6 +1849,10 @@ static napi_value init(napi_env env, napi_value exports) {
         M("encryptSampled", ctx_encrypt_sampled),
         M("decrypt", ctx_decrypt),
         M("addPlain", ctx_add_plain),
+        M("shamirShares", ctx_shamir),
+        M("prepareKeyShares", ctx_share_prep),
+        M("partialDecryptPrepared", ctx_partial_dec),
+        M("combinePartials", ctx_combine),
         M("bootstrap", ctx_bootstrap),
         M("bootstrapPrepared", ctx_bootstrap_prepared),
         M("sampleExtract", ctx_sample_extract),
