@@ -1,6 +1,7 @@
 """Moduli at the edges of the kernel families, and rows that fill the
-unreduced input windows (helpers of test_ntt_primes.py, test_gpu_ranges.py and
-test_gpu_negacyclic.py; plain Python and numpy, no GPU).
+unreduced input windows (helpers of test_ntt_primes.py, test_gpu_ranges.py,
+test_gpu_ranges_stream.py and test_gpu_negacyclic.py; plain Python and numpy,
+no GPU).
 
 The library picks its kernels from the modulus
 (node-fhe-accelerate_amd/csrc/fhe_gpu.cpp, fhe_ctx_create):
@@ -13,6 +14,8 @@ The lazy flag is not part of fhe_ctx_info, so :func:`is_lazy` restates the
 inequality.  :func:`boundary_primes` gives, for one degree, the NTT-friendly
 primes (q = 1 mod 2N) on either side of each of those thresholds, and
 :func:`wrap_prime` the first one at which the lazy forward provably wraps.
+The streaming kernels change arithmetic at q = 2^63 instead:
+:func:`stream_primes` and the word and scalar lists at the end of the file.
 """
 from __future__ import annotations
 
@@ -250,3 +253,77 @@ def weight_rows(n: int, q: int, count: int, period: int, seed: int = 1) -> np.nd
     w[kind == 2] = np.uint64(q)
     w[kind == 3] = np.uint64(M64)
     return w
+
+
+# ---------------------------------------------------------------- streaming kernels: the 2^63 edge
+# The streaming sums (tally.hip, threshold.hip, elementwise.hip) take any
+# degree and switch their word arithmetic at q = 2^63: the Shoup product and
+# the Barrett reduction below, the Montgomery product and one conditional
+# subtraction above (tally_ops.hpp scaled1, fhe_arith.hpp mod64_slow).
+STREAM_NAMES = ("u32_top", "u64_bottom", "u64_top", "wide_bottom", "shoup_top", "wmont_bottom", "u64_max")
+
+
+def stream_primes(n: int) -> dict:
+    """The word-size pair and the top of the 64-bit lanes (as boundary_primes),
+    the bottom of the wide family (q >= 2^62: wide transforms, Shoup scalar
+    product), the primes on either side of 2^63 (shoup_top: the Shoup
+    remainder x s - hi(x s') q reaches up to 2q ~ 2^64; wmont_bottom: the first
+    Montgomery one) and the last prime of the word."""
+    b = boundary_primes(n)
+    return {
+        "u32_top": b["u32_top"],
+        "u64_bottom": b["u64_bottom"],
+        "u64_top": b["u64_top"],
+        "wide_bottom": prime_above(1 << 62, n),
+        "shoup_top": prime_below((1 << 63) - 1, n),
+        "wmont_bottom": prime_above(1 << 63, n),
+        "u64_max": prime_below(M64, n),
+    }
+
+
+def _distinct(values):
+    out = []
+    for v in values:
+        if 0 <= v <= M64 and v not in out:
+            out.append(v)
+    return out
+
+
+def stream_words(q: int) -> list:
+    """Raw input words of the streaming kernels: the residues 0, 1, q-1 and
+    their first and second unreduced copies, the middle of the range, the
+    32-bit and 63-bit carries, and the top of the word (-q, -2, -1 mod 2^64)."""
+    return _distinct([0, 1, q - 1, q, q + 1, 2 * q - 1, 2 * q, 2 * q + 1, q // 2, (1 << 32) - 1, 1 << 32,
+                      (1 << 63) - 1, 1 << 63, (1 << 64) - q, M64 - 1, M64])
+
+
+def stream_scalars(q: int) -> list:
+    """Scalars (weights, lambdas) of the streaming kernels, any u64 read
+    mod q: the residues at both ends, unreduced q and q+1, the middle, the
+    Shoup/Montgomery threshold 2^63, the top of the word and two seeded
+    random words."""
+    rng = np.random.default_rng([q % (1 << 32), q >> 32, 63])
+    return _distinct([0, 1, 2, q - 1, q, q + 1, q // 2, 1 << 63, M64] + [int(v) for v in rng.integers(
+        0, M64, size=2, dtype=np.uint64, endpoint=True)])
+
+
+def cross_ballots(q: int, n: int, polys: int):
+    """(ballots [count, polys, n], scalars [count]), count = |S| |W|, in which
+    every pair of stream_words(q) x stream_scalars(q) meets in every column:
+    ballot i carries scalar S[i % |S|], and word j of its polys * n words is
+    W[(j + i // |S|) % |W|]."""
+    W, S = stream_words(q), stream_scalars(q)
+    count = len(S) * len(W)
+    i = np.arange(count)
+    j = np.arange(polys * n)
+    words = np.array(W, dtype=np.uint64)[(j[None, :] + i[:, None] // len(S)) % len(W)]
+    scalars = np.array(S, dtype=np.uint64)[i % len(S)]
+    return np.ascontiguousarray(words.reshape(count, polys, n)), scalars
+
+
+# Ballot counts of the streaming sums: one, the unroll of 8 and its
+# remainders, two rounds and one (None: the whole of cross_ballots).
+STREAM_COUNTS = (1, 2, 7, 8, 9, 17, None)
+# q = 97: this many terms of 2^64 - 1 leave 98 >= q (residue 1) in the
+# accumulator's high word, which fold128 (tally_ops.hpp) then has to reduce.
+HIGH_WORD_COUNT = 99

@@ -92,7 +92,9 @@ OPS = ("forward", "inverse", "multiply rolled", "multiply squares", "multiply ca
 
 
 def modulus(n, name):
-    return name if isinstance(name, int) else P.sweep_primes(n)[name]
+    if isinstance(name, int):
+        return name
+    return P.sweep_primes(n)[name] if name in P.SWEEP_NAMES else P.stream_primes(n)[name]
 
 
 def operand_rows(n, q, inverse, ppb):
@@ -154,7 +156,8 @@ class Ring:
         # top of the window, one slow word among in-window ones, sparse, raw
         order = ["const lim-1", "mixed one slow word per 16", "sparse alternating", "const 2^64-1",
                  "mixed in-window", "const lim", "sparse last", "const q-1"]
-        self.base = base[[names.index(x) for x in order]]
+        # (q >= 2^62: the window is [0, q), lim-1 and lim are the q-1 and q rows)
+        self.base = base[[names.index(x) for x in order if x in names]]
 
     def cts(self, count, comps, shift=0):
         rows = P.tile_rows(self.base, count * comps + shift)[shift:shift + count * comps]
@@ -277,3 +280,134 @@ def test_dot_is_sum_of_tensors(fg, n, name):
     terms = [R.tensor(a[i], bb[i]) for i in range(count)]
     for j in range(3):
         assert (got[j] == R.arr(R.add(*[t[j] for t in terms]))).all(), j
+
+
+# ------------------------------------------------------------ squaring, threshold decryption, plaintext dot
+# ct_cases, and the composed paths of the wide family, whose true inverses
+# only negacyclic mode uses: 2^64 - 2^32 + 1 and the first prime above 2^63.
+# The tests cut the same operands, so the tensor of one is the cached
+# reference of the next.
+NEW_CASES = CT_CASES + [(1024, QG), (1024, "wmont_bottom")]
+new_cases = pytest.mark.parametrize("n,name", NEW_CASES)
+
+
+def square_operands(R):
+    b = 1 if R.n == 16384 else 2
+    return b, R.cts(b, 2), R.cts(b, 2, shift=3)
+
+
+def difference(R, ct, ref):
+    """ct - ref per component, canonical Python integers."""
+    return [[(int(x) % R.q - int(y) % R.q) % R.q for x, y in zip(ct[j], ref[j])] for j in range(2)]
+
+
+def live(polys):
+    """Every polynomial of the expected value has a nonzero coefficient."""
+    return all(any(p) for p in polys)
+
+
+@new_cases
+def test_square_is_ring_tensor(fg, n, name):
+    """square(ct) = ct (x) ct and squared_difference(ct, ref) = d (x) d,
+    d = ct - ref, with one ref per ciphertext and one shared by all."""
+    R = Ring(fg, n, name)
+    b, x, ref = square_operands(R)
+    got = R.eng.square(x)
+    for i in range(b):
+        exp = R.tensor(x[i], x[i])
+        assert live(exp), i
+        assert (got[i] == np.stack([R.arr(c) for c in exp])).all(), i
+    for rf in (ref, ref[0]) if b > 1 else (ref,):
+        got = R.eng.squared_difference(x, rf)
+        for i in range(b):
+            d = difference(R, x[i], rf if rf.ndim == 2 else rf[i])
+            exp = R.tensor(d, d)
+            assert live(exp), (rf.ndim, i)
+            assert (got[i] == np.stack([R.arr(c) for c in exp])).all(), (rf.ndim, i)
+
+
+@new_cases
+def test_square_relin_is_key_switch_sum(fg, n, name):
+    """The key-switch sum of test_relinearize_is_key_switch_sum applied to the
+    tensor of the difference (its c2 is a canonical word)."""
+    R = Ring(fg, n, name)
+    q, lv = R.q, 2
+    bl = -(-q.bit_length() // lv)
+    b, x, ref = square_operands(R)
+    rlk = R.key(47, lv, 2)
+    ek = fg.EvaluationKey(R.ring, rlk, bl)
+    # square_relin is the same entry point without a ref; at n = 16384 one of the two
+    for rf in (ref,) if n == 16384 else (None, ref):
+        got = R.eng.square_relin(x, ek) if rf is None else R.eng.compute_anomaly_score(x, rf, ek)
+        for i in range(b):
+            d = [[int(v) % q for v in x[i, j]] for j in range(2)] if rf is None else difference(R, x[i], rf[i])
+            c0, c1, c2 = R.tensor(d, d)
+            assert any(c2)
+            for l in range(lv):
+                dg = [(v >> (l * bl)) & ((1 << bl) - 1) for v in c2]
+                c0 = R.add(c0, R.mul(dg, rlk[l, 1]))
+                c1 = R.add(c1, R.mul(dg, rlk[l, 0]))
+            assert any(c0) and any(c1)
+            assert (got[i, 0] == R.arr(c0)).all() and (got[i, 1] == R.arr(c1)).all(), (rf is None, i)
+
+
+@new_cases
+def test_partial_decrypt_and_combine_are_ring_formulas(fg, n, name):
+    """partial_s = c1 share_s for one and for three shares; combining the
+    three with the Lagrange coefficients of the ids (1, 3, 4) opens
+    c0 - c1 (sum_s lambda_s share_s)."""
+    R = Ring(fg, n, name)
+    q, ids = R.q, (1, 3, 4)
+    b, x, _ = square_operands(R)
+    sh = R.cts(1, 3, shift=1)[0]  # raw words: one slow word per 16, sparse, 2^64 - 1
+    shares = [fg.KeyShare(R.ring, i, sh[k]) for k, i in enumerate(ids)]
+    got = R.eng.partial_decrypt(x, shares)
+    assert got.shape == (3, b, n)
+    for k in range(3):
+        for i in range(b):
+            exp = R.mul(x[i, 1], sh[k])
+            assert any(exp)
+            assert (got[k, i] == R.arr(exp)).all(), (k, i)
+    one = R.eng.partial_decrypt(x, shares[:1])
+    assert one.shape == (1, b, n) and (one == got[:1]).all()
+    lam = [1] * 3
+    for k, i in enumerate(ids):
+        for j in ids:
+            if j != i:
+                lam[k] = lam[k] * j * pow(j - i, -1, q) % q
+    assert sum(lam) % q == 1 and all(lam)
+    key = [sum(l * (int(v) % q) for l, v in zip(lam, col)) % q for col in zip(*sh)]
+    if q < 1 << 63:
+        assert fg.lagrange_coefficients(q, ids) == lam
+        res = R.eng.combine_partial_decryptions(x, got, ids, with_phase=True)
+    else:
+        # lagrange_coefficients is the reference's lagrange_coefficient, whose signed Euclid
+        # returns no inverse at q >= 2^63 (fhe_gpu.cpp ref_mod_inverse): (0, 4, 0) for these
+        # ids, pinned here.  The interpolating coefficients go to the kernel directly.
+        assert fg.lagrange_coefficients(q, ids) == [0, 4, 0]
+        res = R.eng.combine_partials(x, got, lam, with_phase=True)
+    delta = q // T
+    for i in range(b):
+        ph = R.add([int(v) for v in x[i, 0]], [-v for v in R.mul(x[i, 1], key)])
+        assert any(ph)
+        assert (res.phase[i] == R.arr(ph)).all(), i
+        if q < 1 << 63:  # above, the noise distance is the reference's wrapping int64 one (test_gpu_ranges_stream.py)
+            rounded = [(c * T + q // 2) // q for c in ph]
+            assert (res.values[i] == np.array([v % T for v in rounded], dtype=np.uint64)).all(), i
+            noise = [abs(c - v * delta % q) for c, v in zip(ph, rounded)]
+            assert int(res.max_noise[i]) == max(q - v if v > q // 2 else v for v in noise), i
+
+
+@new_cases
+def test_dot_plain_is_sum_of_products(fg, n, name):
+    """(sum_i c0_i p_i, sum_i c1_i p_i), count 3."""
+    R = Ring(fg, n, name)
+    count = 3
+    cts = R.cts(count, 2)
+    pts = np.ascontiguousarray(R.cts(count, 1, shift=5)[:, 0])
+    got = R.eng.dot_plain(cts, pts)
+    assert got.shape == (2, n)
+    for j in range(2):
+        exp = R.add(*[R.mul(cts[i, j], pts[i]) for i in range(count)])
+        assert any(exp)
+        assert (got[j] == R.arr(exp)).all(), j

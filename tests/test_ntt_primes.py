@@ -189,3 +189,87 @@ def test_tile_and_weight_rows():
     w = P.weight_rows(4, 17, 13, 3)
     assert (w[0:3] < 17).all() and (w[3:6] == 16).all() and (w[6:9] == 17).all() and (w[9:12] == P.M64).all()
     assert (w[12] < 17).all()
+
+
+# ---------------------------------------------------------------- streaming helpers (the 2^63 edge)
+T63, T64 = 1 << 63, 1 << 64
+
+
+def test_pinned_stream_primes():
+    s = P.stream_primes(16)
+    assert (s["wide_bottom"], s["shoup_top"], s["wmont_bottom"], s["u64_max"]) == (
+        4611686018427388097, 9223372036854775073, 9223372036854776257, 18446744073709551521)
+
+
+@pytest.mark.parametrize("logn", range(2, 17))
+def test_stream_primes_sides(logn):
+    """Each prime is prime, 1 mod 2n, on the stated side of its threshold, and
+    the nearest such prime to it."""
+    n = 1 << logn
+    s = P.stream_primes(n)
+    b = P.boundary_primes(n)
+    assert tuple(s) == P.STREAM_NAMES
+    for name, q in s.items():
+        assert P.is_prime(q) and q % (2 * n) == 1, (logn, name)
+    assert all(s[x] == b[x] for x in ("u32_top", "u64_bottom", "u64_top"))
+    assert s["u32_top"] < 1 << 30 < s["u64_bottom"] < s["u64_top"] < T62 < s["wide_bottom"]
+    assert s["wide_bottom"] < s["shoup_top"] < T63 < s["wmont_bottom"] < s["u64_max"] < T64
+    step = 2 * n
+
+    def none_between(lo, hi):  # no prime of the progression strictly between lo and hi
+        first = lo + (1 - lo) % step
+        if first == lo:
+            first += step
+        return not any(P.is_prime(c) for c in range(first, hi, step))
+
+    assert none_between(s["u32_top"], 1 << 30) and none_between(1 << 30, s["u64_bottom"])
+    assert none_between(s["u64_top"], T62) and none_between(T62, s["wide_bottom"])
+    assert none_between(s["shoup_top"], T63) and none_between(T63, s["wmont_bottom"])
+    assert none_between(s["u64_max"], T64)
+
+
+@pytest.mark.parametrize("q", [17, 97, 1073741689, T62 - 87, 4611686018427388097, 9223372036854775073,
+                               9223372036854776257, 18446744073709551521, P.QG])
+def test_stream_words_and_scalars(q):
+    W, S = P.stream_words(q), P.stream_scalars(q)
+    assert len(set(W)) == len(W) and len(set(S)) == len(S)
+    assert all(0 <= v < T64 for v in W + S)
+    want = [0, 1, q - 1, q, q + 1, 2 * q - 1, 2 * q, 2 * q + 1, q // 2, (1 << 32) - 1, 1 << 32, T63 - 1, T63, T64 - q,
+            T64 - 2, T64 - 1]
+    assert set(W) == {v for v in want if v < T64}
+    assert set(S) >= {0, 1, 2, q - 1, q, q + 1, q // 2, T63, T64 - 1} and len(S) <= 11
+    assert len(S) - len({0, 1, 2, q - 1, q, q + 1, q // 2, T63, T64 - 1}) == 2  # the two random words
+    assert P.stream_scalars(q) == S  # deterministic
+    # both kinds of word on either side of q, and residues 0 and q-1 among both lists
+    for vals in (W, S):
+        assert any(v < q for v in vals) and any(v >= q for v in vals)
+        assert {0, q - 1} <= {v % q for v in vals}
+
+
+@pytest.mark.parametrize("n,q,polys", [(4, 17, 1), (16, 97, 2), (16, 9223372036854775073, 3),
+                                       (16, 18446744073709551521, 1), (4, 9223372036854775837, 2)])
+def test_cross_ballots_hold_the_cross_product(n, q, polys):
+    W, S = P.stream_words(q), P.stream_scalars(q)
+    a, s = P.cross_ballots(q, n, polys)
+    count = len(W) * len(S)
+    assert a.dtype == s.dtype == np.uint64 and a.shape == (count, polys, n) and s.shape == (count,)
+    flat = a.reshape(count, -1)
+    full = {(w, c) for w in W for c in S}
+    for j in range(polys * n):  # every column holds every pair
+        assert {(int(flat[i, j]), int(s[i])) for i in range(count)} == full, j
+    assert [int(v) for v in s[:len(S)]] == S and [int(v) for v in flat[0, :min(len(W), polys * n)]] == W[:polys * n]
+
+
+def test_stream_counts_carry_into_the_high_word():
+    """The sums of the streaming tests leave the 64-bit word: two or more
+    terms of 2^64 - 1 have a non-zero high word, and at q = 97 the count of
+    the all-ones case leaves a high word >= q (fold128 reduces hi too)."""
+    assert P.STREAM_COUNTS == (1, 2, 7, 8, 9, 17, None)
+    full = len(P.stream_words(97)) * len(P.stream_scalars(97))
+    for count in P.STREAM_COUNTS:
+        c = full if count is None else count
+        total = sum(P.M64 for _ in range(c))
+        assert (total >> 64 != 0) == (c > 1), c
+    assert sum(P.M64 for _ in range(P.HIGH_WORD_COUNT)) >> 64 >= 97
+    assert (sum(P.M64 for _ in range(P.HIGH_WORD_COUNT)) >> 64) % 97 != 0  # and its residue is not 0
+    assert full >= P.HIGH_WORD_COUNT
