@@ -303,9 +303,7 @@ size_t ct_dot_ws_bytes(const Plan &p, size_t slices, size_t groups) {
 hipError_t launch_ct_dot(const Plan &p, const void *a, const void *b, bool ptr_table, void *ws, uint64_t *dst,
                          size_t count, size_t per, size_t slices, size_t groups, bool by_component) {
     if (count == 0 || groups == 0) return hipSuccess;
-    if (per == 0 || slices == 0 || (slices - 1) * per >= count || slices * per < count || (ptr_table && groups != 1) ||
-        slices > ((size_t)1 << 30))
-        return hipErrorInvalidValue;
+    if (!slices_ok(count, per, slices, groups, ptr_table, (size_t)1 << 30)) return hipErrorInvalidValue;
     DotLaunch d{a, b, ptr_table ? 1 : 0, ws, dst, count, per, slices, groups, by_component ? 1 : 0, nullptr, nullptr};
     return ctdot_any(p, d);
 }
@@ -375,9 +373,7 @@ k_ct_dot_ntt(const void *__restrict__ a, const void *__restrict__ b, int ptr_tab
 hipError_t launch_ct_dot_ntt(const ModConsts &m, const void *a, const void *b, bool ptr_table, uint64_t *dst, uint32_t n,
                              size_t count, size_t per, size_t slices, size_t groups, hipStream_t s) {
     if (count == 0 || groups == 0) return hipSuccess;
-    if ((n & 1) || !(m.q & 1) || per == 0 || slices == 0 || slices > 65535 || (slices - 1) * per >= count ||
-        slices * per < count || (ptr_table && groups != 1))
-        return hipErrorInvalidValue;
+    if ((n & 1) || !(m.q & 1) || !slices_ok(count, per, slices, groups, ptr_table, 65535)) return hipErrorInvalidValue;
     const size_t half = n / 2;
     const dim3 grid((unsigned)((half + kBlock - 1) / kBlock), (unsigned)slices, (unsigned)(groups < 65535 ? groups : 65535));
     hipLaunchKernelGGL(k_ct_dot_ntt, grid, dim3(kBlock), 0, s, a, b, ptr_table ? 1 : 0, dst, half, count, per, groups, m);

@@ -220,6 +220,7 @@ struct DotPlainLaunch {
     uint64_t *dst;
     size_t count, per, slices, groups;
     size_t *resident;  // non-null: query only
+    int *ws_slots;     // non-null: query only
 };
 
 // Slices one launch keeps resident: workgroups per CU (occupancy query, once
@@ -255,6 +256,10 @@ static hipError_t ctdp_go(const Plan &p, const NttArgs<W> &A, const DotPlainLaun
 template <int LOGN, typename W>
 static hipError_t ctdp_one(const Plan &p, const NttArgs<W> &A, const DotPlainLaunch &d, int is_ntt) {
     constexpr int K = ctdp_key<LOGN, W>();
+    if (d.ws_slots) {
+        *d.ws_slots = ctdp_slots<K, W>();
+        return hipSuccess;
+    }
     if constexpr (sizeof(W) == 4) {
         if (p.lazy) return is_ntt ? ctdp_go<K, W, true, true>(p, A, d) : ctdp_go<K, W, true, false>(p, A, d);
     }
@@ -287,17 +292,18 @@ size_t ct_dot_plain_resident(const Plan &p, int is_ntt) {
 }
 
 size_t ct_dot_plain_ws_bytes(const Plan &p, size_t slices, size_t groups) {
-    const int slots = p.word == 64 && p.logn == 14 ? 3 : 1;  // ctdp_slots
+    int slots = 3;
+    DotPlainLaunch d{};
+    d.ws_slots = &slots;
+    (void)ctdp_any(p, d, 0);
     return groups * slices * slots * ((size_t)1 << p.logn) * (p.word == 32 ? 4 : 8);
 }
 
 hipError_t launch_ct_dot_plain(const Plan &p, const void *cts, const void *pts, bool ptr_table, void *ws, uint64_t *dst,
                                size_t count, size_t per, size_t slices, size_t groups, int is_ntt) {
     if (count == 0 || groups == 0) return hipSuccess;
-    if (per == 0 || slices == 0 || (slices - 1) * per >= count || slices * per < count || (ptr_table && groups != 1) ||
-        slices > ((size_t)1 << 30))
-        return hipErrorInvalidValue;
-    DotPlainLaunch d{cts, pts, ptr_table ? 1 : 0, ws, dst, count, per, slices, groups, nullptr};
+    if (!slices_ok(count, per, slices, groups, ptr_table, (size_t)1 << 30)) return hipErrorInvalidValue;
+    DotPlainLaunch d{cts, pts, ptr_table ? 1 : 0, ws, dst, count, per, slices, groups, nullptr, nullptr};
     return ctdp_any(p, d, is_ntt);
 }
 

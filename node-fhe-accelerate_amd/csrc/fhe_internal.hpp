@@ -191,6 +191,13 @@ hipError_t launch_ml_montmul(const uint64_t consts[7], const uint64_t *a, const 
 // more term.  words even, q odd.
 hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
                          size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s);
+// The slice range every sliced launch (tally, dot, dot_plain) accepts: 1 to
+// max_slices slices of `per` units that cover `count` with none empty; a
+// pointer table addresses one group.
+inline bool slices_ok(size_t count, size_t per, size_t slices, size_t groups, bool ptr_table, size_t max_slices) {
+    return per != 0 && slices != 0 && slices <= max_slices && (slices - 1) * per < count && slices * per >= count &&
+           !(ptr_table && groups != 1);
+}
 // Scaled ciphertext sum (tally.hip k_ct_sum_scaled): launch_ct_sum with ballot
 // i of group g multiplied by the scalar of table entry tab[g count + i] (16
 // bytes each, device memory).  launch_scalar_prep fills `total` entries from

@@ -74,8 +74,8 @@ k_ct_sum(const void *__restrict__ src, uint64_t *__restrict__ out, size_t cols, 
 hipError_t launch_ct_sum(const ModConsts &m, const void *src, bool ptr_table, uint64_t *out, size_t words, size_t count,
                          size_t per, size_t slices, size_t groups, int accumulate, hipStream_t s) {
     if (words == 0 || count == 0 || groups == 0) return hipSuccess;
-    if ((words & 1) || !(m.q & 1) || per == 0 || slices == 0 || slices > 65535 || (slices - 1) * per >= count ||
-        slices * per < count || (ptr_table && groups != 1) || (accumulate && slices != 1))
+    if ((words & 1) || !(m.q & 1) || !slices_ok(count, per, slices, groups, ptr_table, 65535) ||
+        (accumulate && slices != 1))
         return hipErrorInvalidValue;
     const size_t cols = words / 2;
     size_t gx = (cols + kBlock - 1) / kBlock;
@@ -193,8 +193,8 @@ hipError_t launch_ct_sum_scaled(const ModConsts &m, const void *src, bool ptr_ta
                                 size_t words, size_t count, size_t per, size_t slices, size_t groups, int accumulate,
                                 hipStream_t s) {
     if (words == 0 || count == 0 || groups == 0) return hipSuccess;
-    if ((words & 1) || !(m.q & 1) || per == 0 || slices == 0 || slices > 65535 || (slices - 1) * per >= count ||
-        slices * per < count || (ptr_table && groups != 1) || (accumulate && slices != 1))
+    if ((words & 1) || !(m.q & 1) || !slices_ok(count, per, slices, groups, ptr_table, 65535) ||
+        (accumulate && slices != 1))
         return hipErrorInvalidValue;
     const size_t cols = words / 2;
     size_t gx = (cols + kBlock - 1) / kBlock;
