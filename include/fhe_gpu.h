@@ -431,7 +431,13 @@ int fhe_ct_dot_plain_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, const uint64
  * fhe_sample_extract_batch sample_extract (:594-624): lwe_a [batch][k*n].
  * fhe_key_switch_batch     key_switch (:626-674): ksk_a [in_dim*level][out_dim]
  *   (the `first` polynomials of ksk.keys, entry i*level + l), ksk_b
- *   [in_dim*level] (coefficient 0 of each `second` polynomial). */
+ *   [in_dim*level] (coefficient 0 of each `second` polynomial).  Any q >= 2.
+ *   The result is the reference's, word for word: its running update
+ *   r = (r + q - (digit * key) % q) % q in u64 arithmetic.  Below 2^63 that
+ *   is -sum of the terms (nothing wraps after the raw body's first update);
+ *   at q >= 2^63 the sum r + q - term wraps at 2^64 and the kernels make the
+ *   update entry by entry, in the reference's order, wrap included.  A
+ *   ciphertext without a non-zero digit keeps its body raw. */
 int fhe_glwe_rotate_batch(fhe_ctx *ctx, uint32_t k, const int32_t *rot, const uint64_t *glwe, uint64_t *out,
                           size_t batch, int where);
 int fhe_cmux_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t level, const uint64_t *ggsw_ntt,

@@ -9,7 +9,10 @@
 //                  out_b = b - sum_{i,l} d_il * ksk_b[i,l][0], with the
 //                  reference's u64-wrapping digit * key products, its `digit
 //                  == 0` skip and its raw (unreduced) body when every digit
-//                  is zero.
+//                  is zero.  For q >= 2^63 the reference's running update
+//                  r = (r + q - term) % q wraps at 2^64 and is no longer
+//                  -sum: there the generic kernels make that update entry by
+//                  entry, in the reference's order (ks_step).
 //
 // rotate / sample_extract are HBM gathers.  key_switch is a modular
 // matrix-vector product per ciphertext over a key shared by the batch: a
@@ -97,9 +100,21 @@ __device__ __forceinline__ uint64_t ks_term(uint64_t d, uint64_t key, uint64_t q
     return mod64_slow(d * key, q, mu);
 }
 
+// ((r + q - t) mod 2^64) % q for q >= 2^63, r and t below q (or r the raw
+// body): key_switch's running update (:661, :664) where its u64 sum wraps.
+// The wrapped word is below 2^64 <= 2q, so one subtraction reduces it.
+__device__ __forceinline__ uint64_t ks_step(uint64_t r, uint64_t t, uint64_t q) {
+    const uint64_t x = r + q - t;
+    return x >= q ? x - q : x;
+}
+
 constexpr int kKsCt = 16;     // ciphertexts per workgroup (key rows read once per 16)
 constexpr int kKsChunk = 256; // (i, l) entries staged per LDS round
 
+// LITERAL (q >= 2^63): acc is the reference's running value, updated in entry
+// order with its u64 wrap, and written as it is; else acc = sum of the terms,
+// negated at the end (the same value while r + q - term cannot wrap).
+template <bool LITERAL>
 __global__ void __launch_bounds__(kLweBlock)
 k_key_switch_a(const uint64_t *__restrict__ ksk_a, const uint64_t *__restrict__ lwe_a, uint64_t *__restrict__ out_a,
                uint32_t in_dim, uint32_t out_dim, uint32_t level, uint32_t base_log, size_t batch, uint64_t q,
@@ -130,7 +145,8 @@ k_key_switch_a(const uint64_t *__restrict__ ksk_a, const uint64_t *__restrict__ 
                 for (int c = 0; c < kKsCt; ++c) {
                     const uint64_t d = dig[e][c];
                     if (d == 0) continue;  // uniform across the workgroup
-                    acc[c] = addq(acc[c], ks_term(d, key, q, mu), q);
+                    const uint64_t t = ks_term(d, key, q, mu);
+                    acc[c] = LITERAL ? ks_step(acc[c], t, q) : addq(acc[c], t, q);
                 }
             }
         }
@@ -138,12 +154,14 @@ k_key_switch_a(const uint64_t *__restrict__ ksk_a, const uint64_t *__restrict__ 
     if (j < out_dim) {
 #pragma unroll
         for (int c = 0; c < kKsCt; ++c)
-            if (c0 + c < batch) out_a[(c0 + c) * out_dim + j] = acc[c] == 0 ? 0 : q - acc[c];
+            if (c0 + c < batch) out_a[(c0 + c) * out_dim + j] = LITERAL || acc[c] == 0 ? acc[c] : q - acc[c];
     }
 }
 
 // One wavefront per ciphertext: sum of the body terms and the first
-// non-zero digit (whose update also reduces the raw body).
+// non-zero digit (whose update also reduces the raw body).  q >= 2^63: the
+// reference's update entry by entry instead -- the lanes compute 64 terms at a
+// time, then every lane applies them in order.
 __global__ void __launch_bounds__(64)
 k_key_switch_b(const uint64_t *__restrict__ ksk_b, const uint64_t *__restrict__ lwe_a,
                const uint64_t *__restrict__ lwe_b, uint64_t *__restrict__ out_b, uint32_t in_dim, uint32_t level,
@@ -152,6 +170,25 @@ k_key_switch_b(const uint64_t *__restrict__ ksk_b, const uint64_t *__restrict__ 
     const uint32_t lane = threadIdx.x;
     const uint64_t mask = (1ull << base_log) - 1;
     const uint32_t entries = in_dim * level;
+    if (q >> 63) {  // uniform
+        uint64_t r = lwe_b[c];
+        for (uint32_t e0 = 0; e0 < entries; e0 += 64) {
+            const uint32_t idx = e0 + lane;
+            uint64_t d = 0, t = 0;
+            if (idx < entries) {
+                const uint32_t i = idx / level, l = idx % level;
+                d = (lwe_a[c * in_dim + i] >> ((level - 1 - l) * base_log)) & mask;
+                if (d != 0) t = ks_term(d, ksk_b[idx], q, mu);
+            }
+            const uint32_t ne = entries - e0 < 64u ? entries - e0 : 64u;
+            for (uint32_t k = 0; k < ne; ++k) {
+                const uint64_t dk = __shfl(d, (int)k, 64), tk = __shfl(t, (int)k, 64);
+                if (dk != 0) r = ks_step(r, tk, q);
+            }
+        }
+        if (lane == 0) out_b[c] = r;
+        return;
+    }
     uint64_t s = 0;
     uint32_t first = 0xFFFFFFFFu;
     for (uint32_t idx = lane; idx < entries; idx += 64) {
@@ -350,14 +387,19 @@ hipError_t launch_key_switch(const ModConsts &m, uint32_t base_log, uint32_t lev
                            level, base_log, m.q, m.mu);
         return hipGetLastError();
     }
-    // generic: any q >= 2, any base_log (64-bit remainder per term)
+    // generic: any q >= 2, any base_log (64-bit remainder per term); q >= 2^63
+    // follows the reference's wrapping update literally
     // grid.y <= 65535 workgroups of kKsCt ciphertexts per launch
     const size_t per_launch = (size_t)65535 * kKsCt;
     for (size_t b0 = 0; out_dim > 0 && b0 < batch; b0 += per_launch) {
         const size_t nb = batch - b0 < per_launch ? batch - b0 : per_launch;
         const dim3 grid((out_dim + kLweBlock - 1) / kLweBlock, (unsigned)((nb + kKsCt - 1) / kKsCt));
-        hipLaunchKernelGGL(k_key_switch_a, grid, dim3(kLweBlock), 0, s, ksk_a, lwe_a + b0 * in_dim,
-                           out_a + b0 * out_dim, in_dim, out_dim, level, base_log, nb, m.q, m.mu);
+        if (m.q >> 63)
+            hipLaunchKernelGGL(k_key_switch_a<true>, grid, dim3(kLweBlock), 0, s, ksk_a, lwe_a + b0 * in_dim,
+                               out_a + b0 * out_dim, in_dim, out_dim, level, base_log, nb, m.q, m.mu);
+        else
+            hipLaunchKernelGGL(k_key_switch_a<false>, grid, dim3(kLweBlock), 0, s, ksk_a, lwe_a + b0 * in_dim,
+                               out_a + b0 * out_dim, in_dim, out_dim, level, base_log, nb, m.q, m.mu);
         if (hipError_t e = hipGetLastError()) return e;
     }
     hipLaunchKernelGGL(k_key_switch_b, dim3((unsigned)batch), dim3(64), 0, s, ksk_b, lwe_a, lwe_b, out_b, in_dim, level,

@@ -15,7 +15,9 @@ convolution.  Pure Python ints: only for small cases.
 ``decompose`` .. ``blind_rotate`` restate the TFHE pieces of BootstrapEngine
 over a ring product passed in, with an explicit LWE modulus: the shared
 reference of the CPU checks of ``ref_cpu.c`` (compat product) and of the GPU
-tests of negacyclic blind rotation (true ring product).
+tests of negacyclic blind rotation (true ring product).  ``sample_extract``,
+``key_switch`` (which also counts the updates that wrap past 2^64) and
+``lwe_decrypt`` restate the LWE side the same way.
 """
 from __future__ import annotations
 
@@ -204,7 +206,9 @@ def rot_amount(a, n, lwe_q):
 
 def decompose(poly, q, bl, lv):
     """decompose (:152-185): signed digits of the raw word, most significant
-    level first, a negative digit d - B stored as q - (B - d)."""
+    level first, a negative digit d - B stored as (q - (B - d)) % q in u64
+    arithmetic: below q = B - d the difference wraps at 2^64 before it is
+    reduced, so the word is off the centred digit by 2^64 mod q."""
     base = 1 << bl
     out = []
     for l in range(lv):
@@ -212,7 +216,7 @@ def decompose(poly, q, bl, lv):
         row = []
         for c in poly:
             d = (int(c) >> sh) & (base - 1)
-            row.append((q - (base - d)) % q if d > base // 2 else d)
+            row.append(((q - (base - d)) & M64) % q if d > base // 2 else d)
         out.append(row)
     return out
 
@@ -272,3 +276,71 @@ def blind_rotate(acc, lwe_a, lwe_b, lwe_q, bsk, q, bl, lv, k=1, mul=polymul):
         rot = [rotate(p, a_rot, q) for p in acc]
         acc = cmux(bsk[i], acc, rot, q, bl, lv, k, mul)
     return acc
+
+
+def sample_extract(glwe, q):
+    """sample_extract (:594-624) of glwe [k+1][n] -> (a [k n], b): a[i n] =
+    mask_i[0] and the body b = body[0] are copied raw; a[i n + j] =
+    ((q - mask_i[n - j]) mod 2^64) % q for j > 0 (:616)."""
+    k, n = len(glwe) - 1, len(glwe[0])
+    a = []
+    for i in range(k):
+        m = [int(v) for v in glwe[i]]
+        a.append(m[0])
+        a.extend(((q - m[n - j]) & M64) % q for j in range(1, n))
+    return a, int(glwe[k][0])
+
+
+def key_switch(ksk_a, ksk_b, lwe_a, lwe_b, q, bl, lv, out_dim=None, skip_first_body=False):
+    """key_switch (:626-674) -> (a [out_dim], b, mask_wraps, body_wraps).
+
+    ksk_a [in_dim lv][out_dim], ksk_b [in_dim lv], entry i lv + l.  Digit
+    (coeff >> (lv - 1 - l) bl) & (B - 1) of the raw mask word (:649-650); a
+    zero digit skips its entry (:652-655); every other one updates
+      a[j] = (a[j] + q - (digit * key_a[j]) % q) % q        (:661)
+      b    = (b    + q - (digit * key_b)    % q) % q        (:664)
+    in u64 arithmetic: the product wraps at 2^64, and so does the sum
+    r + q - term, which passes 2^64 only when q > 2^63 or when r is the raw
+    body (>= q) in its first update.  The body starts as the raw lwe_b (:640)
+    and is returned raw when every digit is zero.
+
+    mask_wraps / body_wraps count the updates whose sum passed 2^64;
+    skip_first_body leaves the first body update (the one that meets the raw
+    body) out of body_wraps.  out_dim is only needed without key rows."""
+    if out_dim is None:
+        out_dim = len(ksk_a[0])
+    mask = (1 << bl) - 1
+    ra, rb = [0] * out_dim, int(lwe_b)
+    mask_wraps = body_wraps = 0
+    first = True
+    idx = 0
+    for c in lwe_a:
+        c = int(c)
+        for l in range(lv):
+            d = (c >> ((lv - 1 - l) * bl)) & mask
+            if d == 0:
+                idx += 1
+                continue
+            row = ksk_a[idx] if out_dim else ()
+            for j in range(out_dim):
+                s = ra[j] + q - ((d * int(row[j])) & M64) % q
+                mask_wraps += s > M64
+                ra[j] = (s & M64) % q
+            s = rb + q - ((d * int(ksk_b[idx])) & M64) % q
+            if not (first and skip_first_body):
+                body_wraps += s > M64
+            first = False
+            rb = (s & M64) % q
+            idx += 1
+    return ra, rb, mask_wraps, body_wraps
+
+
+def lwe_decrypt(sk, lwe_a, lwe_b, q, t):
+    """The library's LWE decryption (include/fhe_gpu.h, fhe_lwe_decrypt_batch)
+    -> (value, phase): phase = b - sum_j a_j s_j mod q over the integers (s_j
+    any int64, a_j and b raw words), value = ((phase t + q / 2) / q) % t with
+    decode_plaintext's 128-bit numerator (encryption.cpp:136-149: nothing
+    wraps) and its t == 0 -> 4 (:138)."""
+    t = t if t else 4
+    p = (int(lwe_b) - sum(int(a) * int(s) for a, s in zip(lwe_a, sk))) % q
+    return ((p * t + q // 2) // q) % t, p

@@ -950,7 +950,8 @@ void oracle_lwe_decrypt(u64 q, u64 t, const int64_t *sk, u32 dim, const u64 *a, 
         const u64 kq = sk[j] < 0 && mag ? q - mag : mag;
         s = (u64)(((u128)s + (u64)((u128)(a[j] % q) * kq % q)) % q);
     }
-    const u64 p = (b % q + q - s) % q;
+    const u64 br = b % q;
+    const u64 p = br >= s ? br - s : br + (q - s); /* exact: br + q - s passes 2^64 at q > 2^63 */
     if (phase) *phase = p;
     if (value) *value = (u64)(((u128)p * ee_t(t) + q / 2) / q) % ee_t(t);
 }
