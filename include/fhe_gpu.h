@@ -437,7 +437,34 @@ int fhe_ct_dot_plain_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, const uint64
  *   is -sum of the terms (nothing wraps after the raw body's first update);
  *   at q >= 2^63 the sum r + q - term wraps at 2^64 and the kernels make the
  *   update entry by entry, in the reference's order, wrap included.  A
- *   ciphertext without a non-zero digit keeps its body raw. */
+ *   ciphertext without a non-zero digit keeps its body raw.
+ * fhe_slot_extract_batch   the LWE ciphertext at ANY coefficient of an RLWE
+ *   difference, the input of the encrypted comparisons (encryption.cpp
+ *   :1112-1303 stop at "the difference, ready for PBS").  ct [batch][2][n] =
+ *   (c0, c1); ref / ref_count as fhe_ct_square_batch (NULL / 0, one ciphertext
+ *   for the whole batch, or one per ciphertext).  D = mod_sub(ct mod q, ref
+ *   mod q) per word, or ct mod q without a reference; negate != 0: D =
+ *   mod_sub(ref, ct), or -ct.  (D0, D1) is read as the GLWE with mask D1 and
+ *   body D0.  For slot h = slots[s] (each below n; slots may repeat and nslots
+ *   may exceed n): lwe_a [batch][nslots][n], lwe_a[j] = D1[h - j] for j <= h
+ *   and (q - D1[n + h - j]) % q for j > h; lwe_b [batch][nslots] =
+ *   (D0[h] + offsets[s] mod q) mod q.  Every output word is canonical.  These
+ *   are, word for word, fhe_poly_sub_batch (or fhe_poly_neg_batch) on the
+ *   reduced words, fhe_glwe_rotate_batch by -h, fhe_sample_extract_batch and a
+ *   modular add on the body, in one launch that reads ct and ref once.  slots
+ *   and offsets (any u64; NULL = zeros) are HOST arrays in both residences,
+ *   copied before the call returns.  Every context: any n, any odd q < 2^64,
+ *   either mode (no transform runs).  FHE_ERR_INVALID_ARG: a null ct, slots,
+ *   lwe_a or lwe_b, nslots == 0, batch == 0, a ref_count other than 0, 1 or
+ *   batch, "slot index out of range" for a slot >= n, an output that overlaps
+ *   ct or ref.  A multi-device context splits the batch.
+ * fhe_lwe_sum_batch        the sum of LWE ciphertexts of any dimension (no
+ *   context): lwe_a [terms][batch][dim], lwe_b [terms][batch] -> out_a[c][j] =
+ *   sum_t (a mod q) mod q, out_b[c] = (sum_t (b mod q) + body_offset mod q)
+ *   mod q.  Any q >= 2 (nothing wraps at q >= 2^63), dim >= 0; terms == 0 or
+ *   batch == 0: FHE_ERR_INVALID_ARG.  With the sign bootstrap (the constant
+ *   test polynomial q / t / 2) it turns differences into encrypted bits:
+ *   SIGN(x) + SIGN(-x) is [x == 0], SIGN(x) + q / t / 2 is [x >= 0]. */
 int fhe_glwe_rotate_batch(fhe_ctx *ctx, uint32_t k, const int32_t *rot, const uint64_t *glwe, uint64_t *out,
                           size_t batch, int where);
 int fhe_cmux_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t level, const uint64_t *ggsw_ntt,
@@ -456,6 +483,12 @@ int fhe_br_repair_count(fhe_ctx *ctx, uint64_t *count);
 int fhe_key_switch_batch(uint64_t q, uint32_t base_log, uint32_t level, uint32_t in_dim, uint32_t out_dim,
                          const uint64_t *ksk_a, const uint64_t *ksk_b, const uint64_t *lwe_a, const uint64_t *lwe_b,
                          uint64_t *out_a, uint64_t *out_b, size_t batch, int where, int device, void *hip_stream);
+int fhe_slot_extract_batch(fhe_ctx *ctx, const uint64_t *ct, const uint64_t *ref, size_t ref_count, int negate,
+                           const uint32_t *slots, const uint64_t *offsets, size_t nslots, uint64_t *lwe_a,
+                           uint64_t *lwe_b, size_t batch, int where);
+int fhe_lwe_sum_batch(uint64_t q, uint32_t dim, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t terms,
+                      uint64_t body_offset, uint64_t *out_a, uint64_t *out_b, size_t batch, int where, int device,
+                      void *hip_stream);
 
 /* ---- EncryptionEngine encrypt / decrypt / add_plain (encryption.cpp) ----
  * The reference's RLWE encryption with its encoding: t = plaintext modulus

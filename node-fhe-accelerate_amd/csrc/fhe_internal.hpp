@@ -285,6 +285,23 @@ hipError_t launch_br_add(const ModConsts &m, const uint64_t *cur, const uint64_t
 // sample_extract: glwe [batch][k+1][n] -> lwe_a [batch][k*n], lwe_b [batch]
 hipError_t launch_sample_extract(const ModConsts &m, const uint64_t *glwe, uint64_t *lwe_a, uint64_t *lwe_b,
                                  uint32_t n, uint32_t k, size_t batch, hipStream_t s);
+// Slot extraction (lwe.hip k_slot_extract): the LWE ciphertexts at the
+// coefficients slots[s] of ct - ref (negate: ref - ct; ref nullable, ref_stride
+// in words, 0 shares one ref), bodies plus offsets[s] mod q: ct [batch][2][n]
+// -> lwe_a [batch][nslots][n], lwe_b [batch][nslots].  slots (each below n)
+// and offsets (nullable) are HOST arrays, read before the call returns; beyond
+// kSlotInline slots they go through the device table `tab` of
+// slot_table_bytes(nslots) bytes.
+constexpr int kSlotInline = 16;
+size_t slot_table_bytes(size_t nslots);
+hipError_t launch_slot_extract(const ModConsts &m, const uint64_t *ct, const uint64_t *ref, size_t ref_stride, int negate,
+                               const uint32_t *slots, const uint64_t *offsets, size_t nslots, void *tab,
+                               uint64_t *lwe_a, uint64_t *lwe_b, uint32_t n, size_t batch, hipStream_t s);
+// Sum of LWE ciphertexts: lwe_a [terms][batch][dim], lwe_b [terms][batch] ->
+// out_a [batch][dim], out_b [batch] = sum + body_offset, all mod q (any q >= 2).
+hipError_t launch_lwe_sum(const ModConsts &m, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t terms,
+                          uint64_t body_offset, uint64_t *out_a, uint64_t *out_b, uint32_t dim, size_t batch,
+                          hipStream_t s);
 // LWE key switch (BootstrapEngine::key_switch); scratch of
 // key_switch_scratch_bytes (0: none needed) for the split partial sums.
 size_t key_switch_scratch_bytes(const ModConsts &m, uint32_t base_log, uint32_t level, uint32_t in_dim,

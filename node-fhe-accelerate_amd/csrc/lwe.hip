@@ -95,6 +95,97 @@ k_sample_extract(const uint64_t *__restrict__ glwe, uint64_t *__restrict__ lwe_a
     }
 }
 
+// Slot extraction: the LWE ciphertexts of coefficients h_s of D = ct - ref
+// (or ref - ct, or +-ct without a reference), the RLWE (D0, D1) read as the
+// GLWE (mask D1, body D0).  The words of poly_sub / poly_neg, the rotation by
+// -h_s, sample_extract and a modular add on the body, in one pass: a thread
+// owns SOURCE word i of D1 of one ciphertext, reduces and subtracts it once and
+// writes it to every slot's row, at j = h - i with its sign for i <= h and at
+// j = n + h - i negated above (zero stays zero).  Consecutive i are
+// consecutive j in descending order, so every row is written coalesced, and
+// the 64-bit remainder runs once per source word, not once per output word.
+// D0 is only gathered at the slot indices (thread i takes slots i, i + n, ..).
+// (slot, offset mod q) pairs are wave-uniform scalar loads: from the kernel's
+// own arguments up to kSlotInline slots, from a device table beyond.
+struct SlotArgs {
+    const uint64_t *ct;   // [batch][2][n]
+    const uint64_t *ref;  // nullable; ciphertext c at ref + c ref_stride
+    const uint64_t *tab;  // [nslots][2] (nslots > kSlotInline)
+    uint64_t inl[2 * kSlotInline];
+    uint64_t *lwe_a, *lwe_b;  // [batch][nslots][n], [batch][nslots]
+    size_t ref_stride, batch;
+    uint32_t logn, nslots;
+    int negate;
+    uint64_t q, mu;
+};
+__device__ __forceinline__ uint64_t slot_diff(uint64_t x, const uint64_t *ref, size_t at, int negate, uint64_t q,
+                                              uint64_t mu) {
+    x = red_q(x, q, mu);
+    const uint64_t y = ref ? red_q(ref[at], q, mu) : 0;
+    return negate ? subq(y, x, q) : subq(x, y, q);
+}
+template <bool INLINE>
+__global__ void __launch_bounds__(kLweBlock)
+k_slot_extract(SlotArgs E) {
+    const uint64_t q = E.q, mu = E.mu;
+    const uint32_t n = 1u << E.logn, S = E.nslots;
+    const size_t total = E.batch << E.logn;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) {
+        const size_t c = x >> E.logn;
+        const uint32_t i = (uint32_t)x & (n - 1);
+        const uint64_t *ct = E.ct + c * 2 * n;
+        const uint64_t *ref = E.ref ? E.ref + c * E.ref_stride : nullptr;
+        const uint64_t d = slot_diff(ct[n + i], ref, n + i, E.negate, q, mu);
+        const uint64_t nd = d == 0 ? 0 : q - d;
+        uint64_t *row = E.lwe_a + ((c * S) << E.logn);
+        for (uint32_t s = 0; s < S; ++s, row += n) {
+            const uint32_t h = (uint32_t)(INLINE ? E.inl[2 * s] : E.tab[2 * (size_t)s]);
+            if (i <= h) row[h - i] = d;
+            else row[n + h - i] = nd;
+        }
+        for (uint32_t s = i; s < S; s += n) {
+            const uint32_t h = (uint32_t)(INLINE ? E.inl[2 * s] : E.tab[2 * (size_t)s]);
+            const uint64_t off = INLINE ? E.inl[2 * s + 1] : E.tab[2 * (size_t)s + 1];
+            E.lwe_b[c * S + s] = addq(slot_diff(ct[h], ref, h, E.negate, q, mu), off, q);
+        }
+    }
+}
+// The (slot, offset mod q) table from HOST arrays: the entries travel as kernel
+// arguments, kSlotChunk per launch (no host buffer outlives the call).
+static constexpr int kSlotChunk = 128;
+struct SlotChunk {
+    uint64_t e[2 * kSlotChunk];
+};
+__global__ void __launch_bounds__(kSlotChunk)
+k_slot_table(SlotChunk c, uint64_t *__restrict__ tab, uint32_t count) {
+    const uint32_t i = threadIdx.x;
+    if (i >= count) return;
+    tab[2 * i] = c.e[2 * i];
+    tab[2 * i + 1] = c.e[2 * i + 1];
+}
+
+// out_a[x] = sum_t a[t][x], out_b[c] = sum_t b[t][c] + offset (mod q) over
+// [terms][batch][dim] masks and [terms][batch] bodies: a thread per output
+// word walks the terms, coalesced along the mask index.  Raw words are
+// reduced first; addq does not wrap at q >= 2^63.
+__global__ void __launch_bounds__(kLweBlock)
+k_lwe_sum(const uint64_t *__restrict__ lwe_a, const uint64_t *__restrict__ lwe_b, uint64_t *__restrict__ out_a,
+          uint64_t *__restrict__ out_b, size_t terms, size_t words, size_t batch, uint64_t offset, uint64_t q,
+          uint64_t mu) {
+    const size_t total = words + batch;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) {
+        const bool body = x >= words;
+        const uint64_t *src = body ? lwe_b + (x - words) : lwe_a + x;
+        const size_t step = body ? batch : words;
+        uint64_t acc = body ? offset : 0;
+        for (size_t t = 0; t < terms; ++t) acc = addq(acc, red_q(src[t * step], q, mu), q);
+        if (body) out_b[x - words] = acc;
+        else out_a[x] = acc;
+    }
+}
+
 // ((d * key) mod 2^64) % q  -- key_switch's `(digit * ksk_entry.first[j]) % q`
 __device__ __forceinline__ uint64_t ks_term(uint64_t d, uint64_t key, uint64_t q, uint64_t mu) {
     return mod64_slow(d * key, q, mu);
@@ -344,6 +435,62 @@ hipError_t launch_sample_extract(const ModConsts &m, const uint64_t *glwe, uint6
     if (batch == 0 || k == 0) return hipSuccess;
     hipLaunchKernelGGL(k_sample_extract, dim3(lwe_grid((size_t)batch * k * n)), dim3(kLweBlock), 0, s, glwe, lwe_a,
                        lwe_b, n, k, batch, m.q, m.mu);
+    return hipGetLastError();
+}
+
+size_t slot_table_bytes(size_t nslots) { return nslots > (size_t)kSlotInline ? nslots * 16 : 0; }
+
+hipError_t launch_slot_extract(const ModConsts &m, const uint64_t *ct, const uint64_t *ref, size_t ref_stride, int negate,
+                               const uint32_t *slots, const uint64_t *offsets, size_t nslots, void *tab,
+                               uint64_t *lwe_a, uint64_t *lwe_b, uint32_t n, size_t batch, hipStream_t s) {
+    if (batch == 0 || nslots == 0) return hipSuccess;
+    if (nslots > 0xffffffffull || n == 0 || (n & (n - 1))) return hipErrorInvalidValue;
+    const bool inl = nslots <= (size_t)kSlotInline;
+    if (!inl && !tab) return hipErrorInvalidValue;
+    SlotArgs E;
+    E.ct = ct;
+    E.ref = ref;
+    E.tab = inl ? nullptr : (const uint64_t *)tab;
+    for (int i = 0; i < 2 * kSlotInline; ++i) E.inl[i] = 0;
+    if (inl) {
+        for (size_t i = 0; i < nslots; ++i) {
+            E.inl[2 * i] = slots[i];
+            E.inl[2 * i + 1] = offsets ? offsets[i] % m.q : 0;
+        }
+    } else {
+        for (size_t i0 = 0; i0 < nslots; i0 += kSlotChunk) {
+            const size_t nb = nslots - i0 < (size_t)kSlotChunk ? nslots - i0 : (size_t)kSlotChunk;
+            SlotChunk c = {};
+            for (size_t i = 0; i < nb; ++i) {
+                c.e[2 * i] = slots[i0 + i];
+                c.e[2 * i + 1] = offsets ? offsets[i0 + i] % m.q : 0;
+            }
+            hipLaunchKernelGGL(k_slot_table, dim3(1), dim3(kSlotChunk), 0, s, c, (uint64_t *)tab + 2 * i0, (uint32_t)nb);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+    }
+    E.lwe_a = lwe_a;
+    E.lwe_b = lwe_b;
+    E.ref_stride = ref_stride;
+    E.batch = batch;
+    E.logn = (uint32_t)__builtin_ctz(n);
+    E.nslots = (uint32_t)nslots;
+    E.negate = negate ? 1 : 0;
+    E.q = m.q;
+    E.mu = m.mu;
+    const dim3 grid(lwe_grid(batch * n));
+    if (inl) hipLaunchKernelGGL(k_slot_extract<true>, grid, dim3(kLweBlock), 0, s, E);
+    else hipLaunchKernelGGL(k_slot_extract<false>, grid, dim3(kLweBlock), 0, s, E);
+    return hipGetLastError();
+}
+
+hipError_t launch_lwe_sum(const ModConsts &m, const uint64_t *lwe_a, const uint64_t *lwe_b, size_t terms,
+                          uint64_t body_offset, uint64_t *out_a, uint64_t *out_b, uint32_t dim, size_t batch,
+                          hipStream_t s) {
+    if (batch == 0 || terms == 0) return hipSuccess;
+    const size_t words = batch * dim;
+    hipLaunchKernelGGL(k_lwe_sum, dim3(lwe_grid(words + batch)), dim3(kLweBlock), 0, s, lwe_a, lwe_b, out_a, out_b,
+                       terms, words, batch, body_offset % m.q, m.q, m.mu);
     return hipGetLastError();
 }
 

@@ -151,6 +151,10 @@ SIGNATURES = [
     ("fhe_key_switch_batch", C.c_int,
      [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int,
       C.c_int, vp]),
+    ("fhe_slot_extract_batch", C.c_int,
+     [vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), u64p, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_lwe_sum_batch", C.c_int,
+     [C.c_uint64, C.c_uint32, vp, vp, C.c_size_t, C.c_uint64, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
     ("fhe_secret_key_prepare", C.c_int, [vp, vp, vp, C.c_int]),
     ("fhe_public_key_prepare", C.c_int, [vp, vp, vp, C.c_int]),
     ("fhe_encrypt_batch", C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int]),
@@ -1777,6 +1781,171 @@ class BootstrapEngine:
         _check(lib().fhe_key_switch_batch(q, base_log, level, in_dim, out_dim, bka.ptr, bkb.ptr, bla.ptr, blb.ptr,
                                           boa.ptr, bob.ptr, nb, w, device, s))
         return out_a, out_b
+
+    def slot_extract(self, cts, slots, offsets=None, ref=None, negate: bool = False, out=None):
+        """The LWE ciphertexts at coefficients `slots` of cts - ref (negate:
+        ref - cts; ref None, one ciphertext [2, n] or the shape of cts), the
+        RLWE (c0, c1) read as the GLWE (mask c1, body c0), bodies plus
+        offsets[s] mod q (fhe_slot_extract_batch): cts [..., 2, n] ->
+        (a [..., S, n], b [..., S]).  The words of subtract (or negate),
+        multiply_glwe_by_monomial by -slot, sample_extract and a modular add
+        on the body, in one launch.  out: an (a, b) pair to write into."""
+        r = self.ring
+        if self.k != 1:
+            raise FHEError(-9, "slot_extract takes RLWE ciphertexts (k = 1)")
+        cts = _as_u64(cts)
+        nb = _lead(cts, (2, r.degree))
+        slots = [int(s) for s in slots]
+        S = len(slots)
+        if any(s < 0 or s >= 1 << 32 for s in slots):
+            raise FHEError(-9, "slot index out of range")
+        if offsets is not None:
+            offsets = [int(o) & ((1 << 64) - 1) for o in offsets]
+            if len(offsets) != S:
+                raise FHEError(-9, "one offset per slot")
+        be, cnt = None, 0
+        if ref is not None:
+            ref = _as_u64(ref)
+            if tuple(ref.shape) == (2, r.degree):
+                be, cnt = _Buf(ref), 1
+            elif tuple(ref.shape) == tuple(cts.shape):
+                be, cnt = _Buf(ref), nb
+            else:
+                raise FHEError(-9, "ciphertext shapes differ")
+        lead = tuple(cts.shape[:-2])
+        a, b = out if out is not None else (_empty(cts, lead + (S, r.degree)), _empty(cts, lead + (S,)))
+        bc, ba, bb = _Buf(cts), _Buf(a, True), _Buf(b, True)
+        if ba.count != nb * S * r.degree or bb.count != nb * S:
+            raise FHEError(-9, "outputs must be [..., S, n] and [..., S]")
+        w = _where(bc, be, ba, bb)
+        r._bind_stream(w)
+        _check(lib().fhe_slot_extract_batch(r._h, bc.ptr, be.ptr if be else None, cnt, int(bool(negate)),
+                                            (C.c_uint32 * max(1, S))(*slots),
+                                            (C.c_uint64 * max(1, S))(*offsets) if offsets is not None else None, S,
+                                            ba.ptr, bb.ptr, nb, w))
+        return a, b
+
+    @staticmethod
+    def lwe_sum(q: int, lwe_a, lwe_b, body_offset: int = 0, device: int = 0, out=None):
+        """Sum over the leading axis of LWE ciphertexts (fhe_lwe_sum_batch):
+        lwe_a [terms, ..., dim], lwe_b [terms, ...] -> (a [..., dim], b [...]),
+        b = sum + body_offset, all mod q."""
+        lwe_a, lwe_b = _as_u64(lwe_a), _as_u64(lwe_b)
+        if len(lwe_a.shape) < 2 or tuple(lwe_a.shape[:-1]) != tuple(lwe_b.shape):
+            raise FHEError(-9, "LWE masks must be [terms, ..., dim] and bodies [terms, ...]")
+        terms, dim = int(lwe_a.shape[0]), int(lwe_a.shape[-1])
+        a, b = out if out is not None else (_empty(lwe_a, tuple(lwe_a.shape[1:])), _empty(lwe_b, tuple(lwe_b.shape[1:])))
+        bla, blb, boa, bob = _Buf(lwe_a), _Buf(lwe_b), _Buf(a, True), _Buf(b, True)
+        nb = blb.count // terms if terms else 0
+        if boa.count != nb * dim or bob.count != nb:
+            raise FHEError(-9, "outputs must be [..., dim] and [...]")
+        w = _where(bla, blb, boa, bob)
+        s = _stream_ptr() if w == FHE_DEVICE else None
+        _check(lib().fhe_lwe_sum_batch(q, dim, bla.ptr, blb.ptr, terms, int(body_offset) & ((1 << 64) - 1), boa.ptr,
+                                       bob.ptr, nb, w, device, s))
+        return a, b
+
+
+class Comparisons:
+    """Encrypted comparisons of packed slot values (the fraud-detection surface
+    of encryption.cpp:1112-1303, which stops at "the difference, ready for
+    PBS"): each operation returns, per ciphertext and slot, an LWE ciphertext
+    (a [..., S, dim], b [..., S]) under the bootstrapping key's LWE key whose
+    phase is about delta = q / t when the predicate holds and about 0
+    otherwise (detect_duplicate: delta times the number of matches).
+
+    SIGN(D, off) = slot_extract with body offsets off, key_switch from n to the
+    LWE dimension, bootstrap with the CONSTANT test polynomial h = delta / 2:
+    phase +h for an input phase in [0, q / 2), -h otherwise.  Slot values lie
+    in [0, t / 2); h centres each value in its window.  Both SIGN halves of an
+    operation go through one key switch and one bootstrap, stacked along the
+    batch, and lwe_sum adds them.  bsk_ntt is prepare_ggsw's form; ksk_a
+    [n * ks_level, dim] and ksk_b serve both key switches, as in bootstrap."""
+
+    def __init__(self, ring: NTTProcessor, t: int, bsk_ntt, ksk_a, ksk_b, base_log: int, level: int,
+                 ks_base_log: int, ks_level: int):
+        self.ring, self.t = ring, (t if t else 4)
+        self.bsk_ntt, self.ksk_a, self.ksk_b = bsk_ntt, _as_u64(ksk_a), _as_u64(ksk_b)
+        self.ks_base_log, self.ks_level = ks_base_log, ks_level
+        self.engine = BootstrapEngine(ring, base_log, level, 1)
+        self.dim = int(self.ksk_a.shape[-1])
+        q = ring.modulus
+        self.delta = q // self.t
+        self.half = self.delta // 2
+        tp = np.full(ring.degree, self.half, dtype=np.uint64)
+        self.sign_poly = torch.from_numpy(tp.view(np.int64)).to(self.ksk_a.device) if _is_tensor(self.ksk_a) else tp
+
+    def encode(self, v: int) -> int:
+        """encode_plaintext's word (encryption.cpp:107-115): (v delta mod 2^64) % q."""
+        return ((int(v) * self.delta) & ((1 << 64) - 1)) % self.ring.modulus
+
+    def _sum_signs(self, halves, slots, body_offset):
+        """halves: (cts, ref, negate, offsets) per SIGN term."""
+        r, q, S = self.ring, self.ring.modulus, len(slots)
+        cts0 = _as_u64(halves[0][0])
+        lead = tuple(cts0.shape[:-2])
+        H = len(halves)
+        ea = _empty(cts0, (H,) + lead + (S, r.degree))
+        eb = _empty(cts0, (H,) + lead + (S,))
+        for i, (cts, ref, negate, offs) in enumerate(halves):
+            self.engine.slot_extract(cts, slots, [o % q for o in offs], ref, negate, out=(ea[i], eb[i]))
+        dev = cts0.device.index or 0 if _is_tensor(cts0) else r.device
+        la, lb = BootstrapEngine.key_switch(q, self.ks_base_log, self.ks_level, self.ksk_a, self.ksk_b, ea, eb, dev)
+        sa, sb = self.engine.bootstrap(la, lb, self.bsk_ntt, self.sign_poly, self.ksk_a, self.ksk_b, self.ks_base_log,
+                                       self.ks_level)
+        return BootstrapEngine.lwe_sum(q, sa, sb, body_offset, dev)
+
+    def greater_equal(self, a, b, slots):
+        """[a >= b] per slot: SIGN(a - b, h) + h."""
+        return self._sum_signs([(a, b, False, [self.half] * len(slots))], slots, self.half)
+
+    def greater_than(self, a, b, slots, _negate=False):
+        """[a > b] (compare_greater_than :1174): SIGN(a - b, h - delta) + h."""
+        return self._sum_signs([(a, b, _negate, [self.half - self.delta] * len(slots))], slots, self.half)
+
+    def less_than(self, a, b, slots):
+        """[a < b] (compare_less_than :1197-1204): greater_than(b, a), the
+        difference negated in the extraction."""
+        return self.greater_than(a, b, slots, _negate=True)
+
+    def check_threshold(self, tally, thresholds, slots):
+        """[tally >= thresholds[s]] per slot (check_threshold :1112-1143):
+        SIGN(tally, h - encode(thr[s])) + h."""
+        if len(thresholds) != len(slots):
+            raise FHEError(-9, "one threshold per slot")
+        return self._sum_signs([(tally, None, False, [self.half - self.encode(v) for v in thresholds])], slots,
+                               self.half)
+
+    def equal(self, a, b, slots):
+        """[a == b] (compare_equal :1206): SIGN(a - b, h) + SIGN(b - a, h)."""
+        offs = [self.half] * len(slots)
+        return self._sum_signs([(a, b, False, offs), (a, b, True, offs)], slots, 0)
+
+    def check_range(self, ct, lo: int, hi: int, slots):
+        """[lo <= ct <= hi] (check_range :1228): SIGN(ct, h - encode(lo)) +
+        SIGN(-ct, h + encode(hi)).  lo <= hi: with an empty range both terms
+        would be -h and the sum would leave the {0, delta} encoding."""
+        if lo > hi:
+            raise FHEError(-9, "check_range needs min <= max")
+        S = len(slots)
+        return self._sum_signs([(ct, None, False, [self.half - self.encode(lo)] * S),
+                                (ct, None, True, [self.half + self.encode(hi)] * S)], slots, 0)
+
+    def detect_duplicate(self, new, existing, slots):
+        """The number of `existing` ciphertexts equal to `new` per slot
+        (detect_duplicate :1293-1300, "add the equality tests"): the 2 count
+        SIGN terms of equal(new, existing_i) in one sum.  An empty list gives
+        the all-zero LWE."""
+        offs = [self.half] * len(slots)
+        if len(existing) == 0:
+            new = _as_u64(new)
+            lead = tuple(new.shape[:-2]) + (len(slots),)
+            if _is_tensor(new):
+                return (torch.zeros(lead + (self.dim,), dtype=new.dtype, device=new.device),
+                        torch.zeros(lead, dtype=new.dtype, device=new.device))
+            return np.zeros(lead + (self.dim,), dtype=np.uint64), np.zeros(lead, dtype=np.uint64)
+        halves = [(new, e, neg, offs) for e in existing for neg in (False, True)]
+        return self._sum_signs(halves, slots, 0)
 
 
 def decompose_polynomial(ring: NTTProcessor, poly, base_log: int, level: int, out=None):

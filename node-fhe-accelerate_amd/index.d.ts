@@ -280,6 +280,29 @@ export interface FHEThresholdEngine extends FHEAnomalyEngine {
   combinePartialDecryptionsBatch(cts: Ciphertext[], partials: PartialDecryption[][], t: number): Promise<DecryptionResult[]>;
 }
 
+/** The coefficient (packed slot) a comparison reads; default 0. */
+export interface CompareOptions {
+  slot?: number;
+}
+
+/** Encrypted comparisons (the fraud-detection surface of encryption.cpp:1112-1303,
+ * which stops at "the difference, ready for PBS"): the LWE ciphertext at the slot
+ * of the difference (fhe_slot_extract_batch), a key switch, the sign bootstrap
+ * (constant test polynomial delta / 2) and the sum of the sign terms
+ * (fhe_lwe_sum_batch).  Slot values lie in [0, t / 2).  Each result is a
+ * bootstrapped LWE ciphertext (as bootstrap() returns) that decrypts to 1 when the
+ * predicate holds and 0 otherwise; detectDuplicate to the number of matches;
+ * checkThresholds to one ciphertext per candidate slot j against thresholds[j]. */
+export interface FHECompareEngine extends FHEThresholdEngine {
+  compareGreaterThan(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  compareLessThan(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  compareEqual(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  checkThreshold(tally: Ciphertext, threshold: bigint, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  checkThresholds(tally: Ciphertext, thresholds: bigint[], bk: BootstrapKey): Promise<Ciphertext[]>;
+  checkRange(ct: Ciphertext, min: bigint, max: bigint, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  detectDuplicate(ct: Ciphertext, existing: Ciphertext[], bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -344,8 +367,16 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   computeAnomalyScore(ballot: Ciphertext, expected: Ciphertext, ek: EvaluationKey): Promise<Ciphertext>;
   partialDecryptBatch(cts: Ciphertext[], share: ThresholdKeys['shares'][0]): Promise<PartialDecryption[]>;
   combinePartialDecryptionsBatch(cts: Ciphertext[], partials: PartialDecryption[][], t: number): Promise<DecryptionResult[]>;
-  /** The device buffer behind a handle (this backend's extension). */
-  deviceBuffer(handle: unknown): DeviceBuffer | undefined;
+  compareGreaterThan(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  compareLessThan(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  compareEqual(a: Ciphertext, b: Ciphertext, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  checkThreshold(tally: Ciphertext, threshold: bigint, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  checkThresholds(tally: Ciphertext, thresholds: bigint[], bk: BootstrapKey): Promise<Ciphertext[]>;
+  checkRange(ct: Ciphertext, min: bigint, max: bigint, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  detectDuplicate(ct: Ciphertext, existing: Ciphertext[], bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  /** The device buffer behind a handle (this backend's extension); part names another
+   * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
+  deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
 }
 
 /** createEngine (src/index.ts:108): a preset name or custom parameters. */
@@ -447,6 +478,17 @@ export declare class NttContext {
     phase?: Words): Words;
   combinePartialsAsync(t: bigint, ct: Words, partials: Words, lambdas: BigUint64Array, values: Words, maxNoise: Words,
     phase?: Words): Promise<Words>;
+  /** lweA [batch][S][n], lweB [batch][S] = the LWE ciphertexts at the coefficients `slots` of
+   * ct - ref (negate: ref - ct; ref as ctSquare), bodies plus offsets[s] (fhe_slot_extract_batch);
+   * slots and offsets are always host arrays. */
+  slotExtract(ct: Words, ref: Words | null, negate: number, slots: BigUint64Array, offsets: BigUint64Array | null,
+    lweA: Words, lweB: Words): Words;
+  slotExtractAsync(ct: Words, ref: Words | null, negate: number, slots: BigUint64Array, offsets: BigUint64Array | null,
+    lweA: Words, lweB: Words): Promise<Words>;
+  /** outA [batch][dim], outB [batch] = the sum over lweA [terms][batch][dim], lweB [terms][batch]
+   * plus bodyOffset on the body, modulo the ring modulus (fhe_lwe_sum_batch). */
+  lweSum(lweA: Words, lweB: Words, terms: number, bodyOffset: bigint, outA: Words, outB: Words): Words;
+  lweSumAsync(lweA: Words, lweB: Words, terms: number, bodyOffset: bigint, outA: Words, outB: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

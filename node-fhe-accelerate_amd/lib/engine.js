@@ -1060,6 +1060,138 @@ function makeEngineClass(native) {
       });
     }
 
+    // ---- encrypted comparisons (encryption.cpp:1112-1303, which stop at "the
+    // difference, ready for PBS").  SIGN(D, off) = slot extraction with body
+    // offset off, key switch to the LWE key, bootstrap with the constant test
+    // polynomial h = delta / 2: +h for a phase in [0, q/2), -h otherwise.  Slot
+    // values lie in [0, t/2).  The SIGN terms of one operation share one key
+    // switch and one bootstrap call; lweSum adds them and the body offset.
+    // Results are 'lwe' ciphertexts: ~delta when the predicate holds, ~0 else.
+    _half() { return this._delta / 2n; }
+    _enc(v) { return ((u64(v) * this._delta) & M64) % this._q; }
+    _modq(v) { return ((v % this._q) + this._q) % this._q; }
+    _slotOf(options) {
+      const s = options && options.slot !== undefined ? Number(options.slot) : 0;
+      if (!Number.isInteger(s) || s < 0 || s >= this._n) throw new FHEError('slot index out of range', FHEErrorCode.INVALID_PARAMETERS);
+      return s;
+    }
+    /** terms: [{ ct, ref | null, negate, offsets: bigint[] per slot }] -> one 'lwe' Ciphertext per slot */
+    async _signSum(bk, terms, slots, bodyOffset) {
+      const b = this._st(bk, 'BootstrapKey');
+      const n = this._n, dim = b.dim, S = slots.length, H = terms.length;
+      const keyId = terms[0].ct.keyId;
+      if (keyId !== bk.keyId) throw new FHEError('Bootstrap key does not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      const slotWords = BigUint64Array.from(slots, (s) => BigInt(s));
+      const ea = this._buf(H * S * n), eb = this._buf(H * S);
+      for (let i = 0; i < H; i++) {
+        const t = terms[i];
+        const c = this._rlwe(t.ct);
+        const r = t.ref ? this._rlwe(t.ref) : null;
+        if (c.comps !== 2 || (r && r.comps !== 2)) throw new FHEError('comparisons take degree-1 ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+        if (r) this._sameKey(t.ct, t.ref, 'compare');
+        await this._ctx.slotExtractAsync(c.buf.view(0, 2 * n), r ? r.buf.view(0, 2 * n) : null, t.negate ? 1 : 0, slotWords,
+          BigUint64Array.from(t.offsets, (o) => this._modq(o)), ea.view(i * S * n, S * n), eb.view(i * S, S));
+      }
+      const la = this._buf(H * S * dim), lb = this._buf(H * S);
+      await this._ctx.keySwitchAsync(b.ksBaseLog, b.ksLevel, b.kskA, b.kskB, ea, eb, la, lb);
+      if (!this._signPoly) this._signPoly = this._upload(new BigUint64Array(n).fill(this._half()));
+      const sa = this._buf(H * S * dim), sb = this._buf(H * S);
+      await this._ctx.bootstrapPreparedAsync(la, lb, b.bskPrep, this._signPoly, b.kskA, b.kskB, b.baseLog, b.level,
+        b.ksBaseLog, b.ksLevel, sa, sb);
+      const oa = this._buf(S * dim), ob = this._buf(S);
+      await this._ctx.lweSumAsync(sa, sb, H, this._modq(bodyOffset), oa, ob);
+      for (const x of [ea, eb, la, lb, sa, sb]) x.free();
+      const out = [];
+      for (let s = 0; s < S; s++) {
+        const o = this._buf(dim + 1);
+        o.copyFrom(oa, 0, s * dim, dim);
+        o.copyFrom(ob, dim, s, 1);
+        out.push(this._lwe(o, keyId, dim));
+      }
+      oa.free();
+      ob.free();
+      return out;
+    }
+    _lwe(buf, keyId, dim) {
+      return this._handle('Ciphertext', { keyId, noiseBudget: this._params.noiseBudget, isNtt: false, degree: 1 },
+        { buf, kind: 'lwe', comps: 0, dim, packed: false });
+    }
+    /** [a > b] (compare_greater_than :1174): SIGN(a - b, h - delta) + h */
+    async compareGreaterThan(a, b, bk, options) {
+      this._check();
+      return guard(async () => {
+        const h = this._half();
+        return (await this._signSum(bk, [{ ct: a, ref: b, negate: false, offsets: [h - this._delta] }], [this._slotOf(options)], h))[0];
+      });
+    }
+    /** [a < b] (compare_less_than :1197-1204): compareGreaterThan(b, a), the difference negated in the extraction */
+    async compareLessThan(a, b, bk, options) {
+      this._check();
+      return guard(async () => {
+        const h = this._half();
+        return (await this._signSum(bk, [{ ct: a, ref: b, negate: true, offsets: [h - this._delta] }], [this._slotOf(options)], h))[0];
+      });
+    }
+    /** [a == b] (compare_equal :1206): SIGN(a - b, h) + SIGN(b - a, h) */
+    async compareEqual(a, b, bk, options) {
+      this._check();
+      return guard(async () => {
+        const h = this._half();
+        return (await this._signSum(bk, [{ ct: a, ref: b, negate: false, offsets: [h] },
+          { ct: a, ref: b, negate: true, offsets: [h] }], [this._slotOf(options)], 0n))[0];
+      });
+    }
+    /** [tally >= threshold] (check_threshold :1112-1143): SIGN(tally, h - encode(threshold)) + h */
+    async checkThreshold(tally, threshold, bk, options) {
+      this._check();
+      return guard(async () => {
+        const h = this._half();
+        return (await this._signSum(bk, [{ ct: tally, ref: null, negate: false, offsets: [h - this._enc(threshold)] }],
+          [this._slotOf(options)], h))[0];
+      });
+    }
+    /** check_threshold per candidate: thresholds[j] against slot j, one LWE per candidate from one extraction */
+    async checkThresholds(tally, thresholds, bk) {
+      this._check();
+      return guard(async () => {
+        if (!Array.isArray(thresholds) || thresholds.length === 0 || thresholds.length > this._n) {
+          throw new FHEError('thresholds must be a non-empty bigint[] of at most polyDegree entries', FHEErrorCode.INVALID_PARAMETERS);
+        }
+        const h = this._half();
+        return this._signSum(bk, [{ ct: tally, ref: null, negate: false, offsets: thresholds.map((v) => h - this._enc(v)) }],
+          thresholds.map((_, j) => j), h);
+      });
+    }
+    /** [min <= ct <= max] (check_range :1228): SIGN(ct, h - encode(min)) + SIGN(-ct, h + encode(max)) */
+    async checkRange(ct, min, max, bk, options) {
+      this._check();
+      return guard(async () => {
+        // an empty range would make both terms -h: the sum would leave the {0, delta} encoding
+        if (BigInt(min) > BigInt(max)) throw new FHEError('checkRange needs min <= max', FHEErrorCode.INVALID_PARAMETERS);
+        const h = this._half();
+        return (await this._signSum(bk, [{ ct, ref: null, negate: false, offsets: [h - this._enc(min)] },
+          { ct, ref: null, negate: true, offsets: [h + this._enc(max)] }], [this._slotOf(options)], 0n))[0];
+      });
+    }
+    /** the number of `existing` ballots equal to `ct` (detect_duplicate :1293-1300: the equality tests added) */
+    async detectDuplicate(ct, existing, bk, options) {
+      this._check();
+      return guard(async () => {
+        if (!Array.isArray(existing)) throw new FHEError('existing must be a Ciphertext[]', FHEErrorCode.INVALID_PARAMETERS);
+        const slot = this._slotOf(options), h = this._half();
+        if (existing.length === 0) {
+          const b = this._st(bk, 'BootstrapKey');
+          this._rlwe(ct);
+          return this._lwe(this._upload(new BigUint64Array(b.dim + 1)), ct.keyId, b.dim);
+        }
+        const terms = [];
+        for (const e of existing) {
+          terms.push({ ct, ref: e, negate: false, offsets: [h] }, { ct, ref: e, negate: true, offsets: [h] });
+        }
+        return (await this._signSum(bk, terms, [slot], 0n))[0];
+      });
+    }
+
     // ---- serialisation: binary = header words + the native words, checksum = SHA-256
     _serialize(kind, h, words, meta, opts) {
       const fmt = (opts && opts.format) || 'binary';
@@ -1180,7 +1312,14 @@ function makeEngineClass(native) {
     /** the native context (NttContext) for batched array-level work */
     get context() { return this._ctx; }
     /** the DeviceBuffer behind a handle (advanced use: batched kernels) */
-    deviceBuffer(h) { const s = h && state.get(h); return s ? s.buf : undefined; }
+    /** the device buffer behind a handle; `part` names another native buffer of
+     *  it (a bootstrap key's 'kskA' / 'kskB') */
+    deviceBuffer(h, part) {
+      const s = h && state.get(h);
+      if (!s) return undefined;
+      if (part === undefined) return s.buf;
+      return s[part] instanceof DeviceBuffer ? s[part] : undefined;
+    }
     dispose() {
       if (!this._disposed) {
         this._disposed = true;

@@ -1613,6 +1613,70 @@ static napi_value ctx_key_switch(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[6], k.argv + 2, 6);
 }
 
+/* slotExtract(ct [batch][2][n], ref | null ([2][n] or [batch][2][n]), negate, slots (host BigUint64Array),
+ * offsets (host BigUint64Array | null), lweA [batch][S][n], lweB [batch][S]): the LWE ciphertexts at the
+ * coefficients `slots` of ct - ref (negate: ref - ct), bodies plus offsets (fhe_slot_extract_batch) */
+static int run_slot_extract(job *j) {
+    const size_t ns = (size_t)j->v[0];
+    return fhe_slot_extract_batch(j->c, j->p[0], j->p[1], (size_t)j->v[1], (int)j->v[2],
+                                  (const uint32_t *)(j->owned + ns), j->v[3] ? j->owned : NULL, ns, j->p[2], j->p[3],
+                                  j->batch, j->where);
+}
+static napi_value ctx_slot_extract(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "slotExtract(ct [batch*2n], ref | null, negate, slots (BigUint64Array), offsets (BigUint64Array) | null, "
+        "lweA [batch*S*n], lweB [batch*S])";
+    call k;
+    if (call_begin(env, info, 7, &k)) return NULL;
+    uint64_t *ct, *ref = NULL, neg, *sl, *of = NULL, *a, *b;
+    size_t nct, nref = 0, nsl, nof = 0, na, nb;
+    if (arr_arg(env, &k, 0, &ct, &nct) || (!undef_arg(env, &k, 1) && arr_arg(env, &k, 1, &ref, &nref)) ||
+        num_arg(env, &k, 2, &neg) || k.argc < 5 || get_u64_array(env, k.argv[3], &sl, &nsl) ||
+        (!undef_arg(env, &k, 4) && get_u64_array(env, k.argv[4], &of, &nof)) || arr_arg(env, &k, 5, &a, &na) ||
+        arr_arg(env, &k, 6, &b, &nb) || nct == 0 || nct % (2 * k.n) || nref % (2 * k.n) || nsl == 0)
+        return bad_args(env, usage), NULL;
+    const size_t batch = nct / (2 * k.n);
+    if ((of && nof != nsl) || na != batch * nsl * k.n || nb != batch * nsl)
+        return range_err(env, "offsets [S], lweA [batch][S][n], lweB [batch][S]");
+    for (size_t i = 0; i < nsl; ++i)
+        if (sl[i] >= k.n) return range_err(env, "slot index out of range");
+    job *j = job_new(&k, run_slot_extract, NULL);
+    j->owned = (uint64_t *)malloc(nsl * 8 + nsl * 4);
+    uint32_t *s32 = (uint32_t *)(j->owned + nsl);
+    for (size_t i = 0; i < nsl; ++i) {
+        j->owned[i] = of ? of[i] : 0;
+        s32[i] = (uint32_t)sl[i];
+    }
+    j->p[0] = ct; j->p[1] = ref; j->p[2] = a; j->p[3] = b;
+    j->v[0] = nsl; j->v[1] = nref / (2 * k.n); j->v[2] = neg ? 1 : 0; j->v[3] = of ? 1 : 0; j->batch = batch;
+    napi_value keep[4] = {k.argv[0], k.argv[5], k.argv[6], k.argv[1]};
+    return job_go(env, &k, j, k.argv[5], keep, ref ? 4 : 3);
+}
+
+/* lweSum(lweA [terms][batch][dim], lweB [terms][batch], terms, bodyOffset, outA [batch][dim], outB [batch]):
+ * the sum of LWE ciphertexts plus a body offset, modulo the ring modulus (fhe_lwe_sum_batch) */
+static int run_lwe_sum(job *j) {
+    fhe_ctx_info ci;
+    fhe_ctx_get_info(j->c, &ci);
+    return fhe_lwe_sum_batch(ci.q, (uint32_t)j->v[0], j->p[0], j->p[1], (size_t)j->v[1], j->v[2], j->p[2], j->p[3],
+                             j->batch, j->where, ci.device, fhe_ctx_stream(j->c));
+}
+static napi_value ctx_lwe_sum(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 6, &k)) return NULL;
+    uint64_t *la, *lb, terms, off, *oa, *ob;
+    size_t nla, nlb, noa, nob;
+    if (arr_arg(env, &k, 0, &la, &nla) || arr_arg(env, &k, 1, &lb, &nlb) || num_arg(env, &k, 2, &terms) ||
+        num_arg(env, &k, 3, &off) || arr_arg(env, &k, 4, &oa, &noa) || arr_arg(env, &k, 5, &ob, &nob) || terms == 0 ||
+        nob == 0 || nlb != terms * nob || noa % nob || nla != terms * noa)
+        return bad_args(env, "lweSum(lweA [terms][batch][dim], lweB [terms][batch], terms, bodyOffset, outA, outB)"), NULL;
+    job *j = job_new(&k, run_lwe_sum, NULL);
+    j->p[0] = la; j->p[1] = lb; j->p[2] = oa; j->p[3] = ob;
+    j->v[0] = noa / nob; j->v[1] = terms; j->v[2] = off; j->batch = nob;
+    napi_value keep[4] = {k.argv[0], k.argv[1], k.argv[4], k.argv[5]};
+    return job_go(env, &k, j, k.argv[4], keep, 4);
+}
+
 /* ---- randomness and key material (fhe_sample_batch, fhe_*_generate) ---- */
 /* sample(kind, seed, stream, noiseStd, out) */
 static int run_sample(job *j) {
@@ -1857,6 +1921,8 @@ static napi_value init(napi_env env, napi_value exports) {
         M("bootstrapPrepared", ctx_bootstrap_prepared),
         M("sampleExtract", ctx_sample_extract),
         M("keySwitch", ctx_key_switch),
+        M("slotExtract", ctx_slot_extract),
+        M("lweSum", ctx_lwe_sum),
         M("sample", ctx_sample),
         M("publicKeyGenerate", ctx_pk_gen),
         M("evalKeyGenerate", ctx_ek_gen),
