@@ -17,7 +17,9 @@ over a ring product passed in, with an explicit LWE modulus: the shared
 reference of the CPU checks of ``ref_cpu.c`` (compat product) and of the GPU
 tests of negacyclic blind rotation (true ring product).  ``sample_extract``,
 ``key_switch`` (which also counts the updates that wrap past 2^64) and
-``lwe_decrypt`` restate the LWE side the same way.
+``lwe_decrypt`` restate the LWE side the same way.  ``decode_noise``,
+``ggsw_gadget``, ``ggsw_encrypt`` and ``ksk_body`` restate the decode epilogue
+of the BFV decryptions and the key generation with their u64 / int64 wraps.
 """
 from __future__ import annotations
 
@@ -344,3 +346,96 @@ def lwe_decrypt(sk, lwe_a, lwe_b, q, t):
     t = t if t else 4
     p = (int(lwe_b) - sum(int(a) * int(s) for a, s in zip(lwe_a, sk))) % q
     return ((p * t + q // 2) // q) % t, p
+
+
+# ---------------------------------------------------------------- decode / key material
+# EncryptionEngine's decode + noise measure and the closed forms of
+# BootstrapEngine's key generation, with the reference's u64 / int64
+# wrap-around spelled out: the second reference of tests/test_engine_edges.py.
+def _i64(x):
+    """(int64_t)x of a wrapped 64-bit word."""
+    x &= M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def decode_noise(p, q, t):
+    """decode_packed (encryption.cpp:150-163) and the distance of
+    compute_noise_budget (:364-400) for a canonical phase p < q -> (value,
+    |noise|).  rounded = (p t + q / 2) / q over a 128-bit numerator (nothing
+    wraps); expected = (rounded delta) % q with the u64 product; the distance
+    is an int64: wrapped to q - noise above q / 2, where (int64_t)q is
+    negative for q >= 2^63 (the sign flip), then |.| taken."""
+    t = t if t else 4
+    delta = q // t
+    r = (p * t + q // 2) // q
+    expected = ((r * delta) & M64) % q
+    noise = _i64(p - expected if p >= expected else expected - p)
+    if noise > _i64(q // 2):
+        noise = _i64(_i64(q) - noise)
+    return r % t, (-noise if noise < 0 else noise) & M64
+
+
+def ggsw_gadget(v, q, l, base_log):
+    """encrypt_ggsw's gadget term (bootstrap_engine.cpp:287-291): (|v| q) >>
+    ((l + 1) base_log) with the u64 product and the shift count taken mod 64;
+    for v < 0 it is (q - g) % q with the subtraction in u64 -- for g > q that
+    wraps and is not the residue of -g."""
+    av = (-v if v < 0 else v) & M64  # |INT64_MIN| = 2^63 as a u64
+    g = ((av * q) & M64) >> (((l + 1) * base_log) & 63)
+    return ((q - g) & M64) % q if v < 0 else g
+
+
+def ksk_body(a_row, lwe_sk, err, glwe_word, q, l, base_log):
+    """One body word of generate_key_switch_key (:367-420): the int64 inner
+    product of the mask row with the LWE key (wrapping), plus the centred
+    error (err > q / 2 reads as err - q, both as int64), reduced with C's
+    truncating % by (int64_t)q -- negative for q >= 2^63 -- then the gadget
+    (glwe_word q) >> ((l + 1) base_log) added in u64 and % q."""
+    ip = sum(int(a) * int(s) for a, s in zip(a_row, lwe_sk)) & M64
+    ev = _i64(err)
+    if ev > _i64(q // 2):
+        ev = _i64(ev - _i64(q))
+    s = _i64(ip + ev)
+    qi = _i64(q)
+    rem = abs(s) % abs(qi)
+    rem = -rem if s < 0 else rem  # C: the remainder takes the dividend's sign
+    gadget = ((int(glwe_word) * q) & M64) >> (((l + 1) * base_log) & 63)
+    return (((rem & M64) + gadget) & M64) % q
+
+
+def compat_polymul(a, b, q):
+    """The ring product as the reference's transforms compute it: polymul
+    below 2^63.  From 2^63 on the signed extended Euclid of
+    ntt_processor.cpp:64-90 reads the modulus as a negative int64 and returns
+    N^-1 = 0, so every inverse transform, and with it every product, is 0."""
+    return polymul(a, b, q) if q < 1 << 63 else [0] * len(a)
+
+
+def ggsw_encrypt(values, sk, masks, err, q, k, base_log, level, mul=compat_polymul):
+    """encrypt_ggsw (:268-306) over given draws -> [count][(k+1) level][k+1][n]
+    as nested lists.  masks [rows][k][n] and err [rows][n] are the uniform and
+    the error draws of the rows (row = c (k+1) level + grp level + l); body =
+    sum_i mask_i * sk + err (encrypt_glwe_zero, :190-227), then the gadget
+    added to coefficient 0 of mask[grp] (grp < k) or of the body."""
+    n = len(sk)
+    sk = [int(x) for x in sk]
+    per = (k + 1) * level
+    out = []
+    for c, v in enumerate(values):
+        ct = []
+        for rr in range(per):
+            r = c * per + rr
+            grp, l = divmod(rr, level)
+            row = [[int(x) for x in masks[r][i]] for i in range(k)]
+            body = [0] * n
+            for i in range(k):
+                body = [(x + y) % q for x, y in zip(body, mul(row[i], sk, q))]
+            body = [(x + int(e)) % q for x, e in zip(body, err[r])]
+            g = ggsw_gadget(int(v), q, l, base_log)
+            if grp < k:
+                row[grp][0] = ((row[grp][0] + g) & M64) % q
+            else:
+                body[0] = ((body[0] + g) & M64) % q
+            ct.append(row + [body])
+        out.append(ct)
+    return out
