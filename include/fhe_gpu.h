@@ -464,7 +464,47 @@ int fhe_ct_dot_plain_ptrs(fhe_ctx *ctx, const uint64_t *const *cts, const uint64
  *   mod q.  Any q >= 2 (nothing wraps at q >= 2^63), dim >= 0; terms == 0 or
  *   batch == 0: FHE_ERR_INVALID_ARG.  With the sign bootstrap (the constant
  *   test polynomial q / t / 2) it turns differences into encrypted bits:
- *   SIGN(x) + SIGN(-x) is [x == 0], SIGN(x) + q / t / 2 is [x >= 0]. */
+ *   SIGN(x) + SIGN(-x) is [x == 0], SIGN(x) + q / t / 2 is [x >= 0].
+ * fhe_lwe_pack_batch       the packing key switch, the way back from the TFHE
+ *   side: nslots LWE ciphertexts per output ciphertext and nslots slot indices
+ *   become ONE BFV ciphertext (c0, c1) whose phase c0 - c1 (*) sk has LWE s's
+ *   message at coefficient slots[s].  (No reference counterpart: its compare_*
+ *   never return from the LWE side.)  pack_key [in_dim*level][2][n], row
+ *   e = i*level + l a pair (c0, c1); lwe_a [batch][nslots][in_dim]; lwe_b
+ *   [batch][nslots]; slots a HOST array [nslots] in both residences, each
+ *   below n, repeats allowed, copied before the call returns; out
+ *   [batch][2][n].  With
+ *     d(s,e)       = (lwe_a[c][s][i] >> ((level-1-l)*base_log)) & (2^base_log - 1)
+ *                    on the raw mask word (key_switch's digit),
+ *     term(s,e,p,j) = ((d * pack_key[e][p][j]) mod 2^64) mod q   (key_switch's
+ *                    product),
+ *     W_s[p][j]    = (-(sum_e term) + [p == 0 and j == 0] * (lwe_b[c][s] mod q))
+ *                    mod q,   h = slots[s],
+ *   out[c][p][j] = sum_s ( j >= h ? W_s[p][j-h] : (q - W_s[p][n+j-h]) % q )
+ *                  (+ out[c][p][j] mod q when accumulate != 0)   mod q.
+ *   The sum is the mathematical sum of canonical terms (no running update that
+ *   could wrap); every output word is canonical; key, mask and body words may
+ *   be any u64.  For q < 2^63 these are, word for word, per (c, s)
+ *   fhe_key_switch_batch with out_dim = 2n (ksk_a = the pack key viewed as
+ *   [in_dim*level][2n], ksk_b = zeros, body 0), a modular add of lwe_b mod q at
+ *   coefficient 0 of the first half, fhe_glwe_rotate_batch (k = 1, mask = the
+ *   second half, body = the first half) by +h, and fhe_ct_sum_batch over the
+ *   slots (polys = 2) -- in one launch without the [batch*nslots][2n] rows.
+ *   Every context: any n, any odd q < 2^64, either mode (no transform runs);
+ *   base_log > 32, q >= 2^63 and moduli without the fast constants take a
+ *   per-term kernel, as key switch does.  1 <= base_log <= 63 and
+ *   (level-1)*base_log < 64, as for relinearisation; nslots * (in_dim*level
+ *   + 1) < 2^31.  FHE_ERR_INVALID_ARG: a null pack_key, lwe_a, lwe_b, slots or
+ *   out, nslots == 0, batch == 0, in_dim == 0 or level == 0, "slot index out
+ *   of range" for a slot >= n, out overlapping an input.  Arguments are checked
+ *   before the context is looked at.  FHE_HOST stages every buffer, the key
+ *   included; a multi-device context splits the batch.  With in_dim = n and the
+ *   ring key's coefficients as the LWE key the same call re-packs chosen slots
+ *   of different ciphertexts (fhe_slot_extract_batch's outputs) into one.
+ *   The key comes from fhe_pack_key_generate (below). */
+int fhe_lwe_pack_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, uint32_t in_dim, const uint64_t *pack_key,
+                       const uint64_t *lwe_a, const uint64_t *lwe_b, const uint32_t *slots, size_t nslots,
+                       int accumulate, uint64_t *out, size_t batch, int where);
 int fhe_glwe_rotate_batch(fhe_ctx *ctx, uint32_t k, const int32_t *rot, const uint64_t *glwe, uint64_t *out,
                           size_t batch, int where);
 int fhe_cmux_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t level, const uint64_t *ggsw_ntt,
@@ -629,7 +669,26 @@ int fhe_bootstrap_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t le
  *   selects 3.2), ksk_b[e] = ((u64)((<a_e, lwe_sk> + e) % (int64)q)
  *   + (glwe_sk[i] q) >> ((l+1) base_log)) % q with the reference's int64 /
  *   u64 wrap-around.  Shift counts >= 64 take the count mod 64.
- * fhe_lwe_decrypt_batch       LWE decryption under an integer key s [dim]:
+ * fhe_pack_key_generate       the key of fhe_lwe_pack_batch: rows =
+ *   lwe_dim*level RLWE encryptions under the ring key sk [n] of the LWE key
+ *   lwe_sk [lwe_dim] times the gadget powers; pack_key [rows][2][n], row
+ *   e = i*level + l = (c0, c1).  c1 = fhe_sample_batch(UNIFORM, seed, stream,
+ *   rows*n) read as [rows][n]; err the same with GAUSSIAN and stream + 1
+ *   (std_dev 0 selects 3.2, as fhe_ksk_generate); c0[e] = c1[e] (*) sk +
+ *   err[e] under the context's transform product, plus m_e on coefficient 0,
+ *   m_e = (|lwe_sk[i]| mod q) * (2^((level-1-l)*base_log) mod q) mod q,
+ *   negated mod q for lwe_sk[i] < 0.  That power is the one the pack's digit
+ *   (a >> ((level-1-l)*base_log)) & (2^base_log - 1) multiplies -- NOT the
+ *   q >> ((l+1) base_log) of fhe_ksk_generate -- so with level*base_log >= the
+ *   bit length of q - 1 the digits recompose the mask word exactly and the
+ *   packed ciphertext decrypts: c0 - c1 (*) sk = X^h (b - <a, lwe_sk>) plus
+ *   the digit-weighted key errors.  The words equal fhe_sample_batch twice,
+ *   fhe_polymul_batch against the broadcast key, fhe_poly_add_batch and the
+ *   gadget add.  1 <= base_log <= 63, (level-1)*base_log < 64.  Slots other
+ *   than 0 decrypt only under FHE_MODE_NEGACYCLIC: compat mode's transform
+ *   product does not commute with the monomial X^h.  Slot 0 decrypts in both
+ *   modes.
+ * fhe_lwe_decrypt_batch      LWE decryption under an integer key s [dim]:
  *   phase = b - sum_j a_j s_j (mod q), values = round(phase t / q) mod t
  *   (decode_plaintext's rounding, encryption.cpp:133-148).  Each output
  *   nullable. */
@@ -653,6 +712,9 @@ int fhe_ggsw_encrypt_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t
 int fhe_ksk_generate(fhe_ctx *ctx, uint32_t base_log, uint32_t level, const uint64_t *glwe_sk, uint32_t n_in,
                      const int64_t *lwe_sk, uint32_t lwe_dim, const uint64_t seed[4], uint64_t stream, double std_dev,
                      uint64_t *ksk_a, uint64_t *ksk_b, int where);
+int fhe_pack_key_generate(fhe_ctx *ctx, uint32_t base_log, uint32_t level, const uint64_t *sk, const int64_t *lwe_sk,
+                          uint32_t lwe_dim, const uint64_t seed[4], uint64_t stream, double std_dev,
+                          uint64_t *pack_key, int where);
 int fhe_lwe_decrypt_batch(uint64_t q, uint64_t t, const int64_t *sk, uint32_t dim, const uint64_t *lwe_a,
                           const uint64_t *lwe_b, uint64_t *values, uint64_t *phase, size_t batch, int where,
                           int device, void *hip_stream);

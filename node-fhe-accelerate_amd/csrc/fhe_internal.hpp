@@ -310,6 +310,18 @@ hipError_t launch_key_switch(const ModConsts &m, uint32_t base_log, uint32_t lev
                              const uint64_t *ksk_a, const uint64_t *ksk_b, const uint64_t *lwe_a,
                              const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch, void *scratch,
                              hipStream_t s);
+// LWE-to-RLWE packing (lwe_pack.hip k_lwe_pack): lwe_a [batch][nslots][in_dim],
+// lwe_b [batch][nslots] and the pack key [in_dim * level][2][n] -> out
+// [batch][2][n] (+ out mod q with accumulate), LWE s at coefficient slots[s].
+// slots (each below n) is a HOST array, read before the call returns; beyond
+// kPackInline slots it goes through the device table `tab` of
+// lwe_pack_table_bytes(nslots) bytes.  nslots * (in_dim * level + 1) < 2^31.
+constexpr int kPackInline = 32;
+size_t lwe_pack_table_bytes(size_t nslots);
+hipError_t launch_lwe_pack(const ModConsts &m, uint32_t base_log, uint32_t level, uint32_t in_dim,
+                           const uint64_t *pack_key, const uint64_t *lwe_a, const uint64_t *lwe_b,
+                           const uint32_t *slots, size_t nslots, int accumulate, void *tab, uint64_t *out, uint32_t n,
+                           size_t batch, hipStream_t s);
 hipError_t launch_decompose(const ModConsts &m, const uint64_t *poly, uint64_t *out, uint32_t n, size_t npoly,
                             uint32_t base_log, uint32_t level, hipStream_t s);
 

@@ -187,6 +187,34 @@ k_ggsw_finish(const uint64_t *__restrict__ prod, const uint64_t *__restrict__ ma
     }
 }
 
+// Pack-key rows (fhe_pack_key_generate): out[e] = (c0, c1) with c0 = prod[e] +
+// err[e] (mod_add on reduced words) and c1 = mask[e], plus at coefficient 0 of
+// c0 the gadget word of row e = i L + l:
+//   (|s_i| mod q) (2^((L-1-l) B) mod q) mod q, negated mod q for s_i < 0
+// -- the power that fhe_lwe_pack_batch's digit (a >> ((L-1-l) B)) & (2^B - 1)
+// multiplies, NOT generate_key_switch_key's q >> ((l+1) B).
+__global__ void __launch_bounds__(kKgBlock)
+k_pack_key_finish(const uint64_t *__restrict__ prod, const uint64_t *__restrict__ masks,
+                  const uint64_t *__restrict__ err, const int64_t *__restrict__ lwe_sk, uint64_t *__restrict__ out,
+                  uint32_t n, uint32_t level, uint32_t base_log, size_t rows, uint64_t q, uint64_t mu, double qinv) {
+    const size_t total = rows * n, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) {
+        const size_t e = x / n;
+        const uint32_t j = (uint32_t)(x % n);
+        uint64_t c0 = addq(red_q(prod[x], q, mu), red_q(err[x], q, mu), q);
+        if (j == 0) {
+            const int64_t v = lwe_sk[e / level];
+            const uint32_t l = (uint32_t)(e % level);
+            const uint64_t av = v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+            uint64_t g = modmul_exact(av, 1ull << ((level - 1 - l) * base_log), q, mu, qinv);
+            if (v < 0 && g) g = q - g;
+            c0 = addq(c0, g, q);
+        }
+        out[(2 * e) * n + j] = c0;
+        out[(2 * e + 1) * n + j] = masks[x];
+    }
+}
+
 // One wavefront per key-switching entry: the int64 inner product (wrapping,
 // as the reference's int64_t accumulation) reduced across lanes.
 __global__ void __launch_bounds__(64)
@@ -249,6 +277,14 @@ hipError_t launch_ggsw_finish(const ModConsts &m, const uint64_t *prod, const ui
     if (rows == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ggsw_finish, dim3(kg_grid(rows * n)), dim3(kKgBlock), 0, s, prod, masks, err, values, out, n, k,
                        level, base_log, rows, m.q, m.mu);
+    return hipGetLastError();
+}
+hipError_t launch_pack_key_finish(const ModConsts &m, const uint64_t *prod, const uint64_t *masks, const uint64_t *err,
+                                  const int64_t *lwe_sk, uint64_t *out, uint32_t n, uint32_t level, uint32_t base_log,
+                                  size_t rows, hipStream_t s) {
+    if (rows == 0 || n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pack_key_finish, dim3(kg_grid(rows * n)), dim3(kKgBlock), 0, s, prod, masks, err, lwe_sk, out, n,
+                       level, base_log, rows, m.q, m.mu, 1.0 / (double)m.q);
     return hipGetLastError();
 }
 hipError_t launch_ksk_body(const ModConsts &m, const uint64_t *glwe_sk, const int64_t *lwe_sk, const uint64_t *a,

@@ -28,6 +28,12 @@ hipError_t launch_modmul_bcast(const ModConsts &m, const uint64_t *x, const uint
 hipError_t launch_ggsw_finish(const ModConsts &m, const uint64_t *prod, const uint64_t *masks, const uint64_t *err,
                               const int64_t *values, uint64_t *out, uint32_t n, uint32_t k, uint32_t level,
                               uint32_t base_log, size_t count, hipStream_t s);
+// Pack-key rows: out [rows][2][n] = (prod + err + gadget word of row e at
+// coefficient 0, masks) from prod, masks, err [rows][n]; rows = lwe_dim * level,
+// row e = i L + l carries lwe_sk[i] 2^((L-1-l) B) mod q.
+hipError_t launch_pack_key_finish(const ModConsts &m, const uint64_t *prod, const uint64_t *masks, const uint64_t *err,
+                                  const int64_t *lwe_sk, uint64_t *out, uint32_t n, uint32_t level, uint32_t base_log,
+                                  size_t rows, hipStream_t s);
 // generate_key_switch_key's bodies (bootstrap_engine.cpp:388-415): entry
 // e = i L + l, b[e] = ((u64)((<a_e, s> + err_e) % (int64)q) + gadget) % q
 hipError_t launch_ksk_body(const ModConsts &m, const uint64_t *glwe_sk, const int64_t *lwe_sk, const uint64_t *a,

@@ -179,6 +179,11 @@ SIGNATURES = [
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, u64p, C.c_uint64, C.c_double, vp, C.c_int]),
     ("fhe_ksk_generate", C.c_int,
      [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, u64p, C.c_uint64, C.c_double, vp, vp, C.c_int]),
+    ("fhe_pack_key_generate", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, u64p, C.c_uint64, C.c_double, vp, C.c_int]),
+    ("fhe_lwe_pack_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), C.c_size_t, C.c_int, vp, C.c_size_t,
+      C.c_int]),
     ("fhe_lwe_decrypt_batch", C.c_int,
      [C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
     ("fhe_modmul_batch", C.c_int, [C.c_uint64, vp, vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
@@ -1045,6 +1050,36 @@ class KeyGenerator:
                                       float(std_dev), ba.ptr, bb.ptr, w))
         return ka, kb
 
+    def pack_key(self, sk, lwe_sk, base_log: int, level: int, stream: int, std_dev: float = 0.0, out=None):
+        """The key of EncryptionEngine.pack_lwe (fhe_pack_key_generate): per
+        LWE key coefficient i and level l an RLWE encryption (c0, c1) under the
+        ring key sk of lwe_sk[i] 2^((level-1-l) base_log) -> PackKey over
+        [dim level, 2, n]."""
+        r = self.ring
+        s = _as_u64(sk.poly if isinstance(sk, SecretKey) else sk)
+        if _is_tensor(lwe_sk):
+            ls = lwe_sk.to(torch.int64).contiguous()
+        else:
+            ls = np.ascontiguousarray(np.asarray(lwe_sk, dtype=np.int64)).view(np.uint64)
+        dim = int(ls.numel() if _is_tensor(ls) else ls.size)
+        out = _empty(s, (dim * level, 2, r.degree)) if out is None else out
+        bs, bl, bo = _Buf(s), _Buf(ls), _Buf(out, True)
+        if bo.count != dim * level * 2 * r.degree:
+            raise FHEError(-9, "pack key must be [dim level, 2, n]")
+        w = _where(bs, bl, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_pack_key_generate(r._h, base_log, level, bs.ptr, bl.ptr, dim, _seed_arr(self.seed), stream,
+                                           float(std_dev), bo.ptr, w))
+        return PackKey(out, base_log, level, dim)
+
+
+class PackKey:
+    """The packing key-switch key [lwe_dim level, 2, n] with its decomposition
+    (KeyGenerator.pack_key; any buffer of that layout serves)."""
+
+    def __init__(self, key, base_log: int, level: int, lwe_dim: int):
+        self.key, self.base_log, self.level, self.lwe_dim = key, base_log, level, lwe_dim
+
 
 def lwe_decrypt(q: int, t: int, sk, lwe_a, lwe_b, device: int = 0):
     """LWE decryption (fhe_lwe_decrypt_batch): (values [batch], phase [batch])."""
@@ -1617,6 +1652,36 @@ class EncryptionEngine:
         """square_relin (:1037-1055)."""
         return self.compute_anomaly_score(ct, None, ek, out)
 
+    def pack_lwe(self, lwe_a, lwe_b, slots, pack_key: "PackKey", out=None, accumulate: bool = False):
+        """The packing key switch (fhe_lwe_pack_batch): LWE ciphertexts
+        (a [..., S, dim], b [..., S]) -- the pair every Comparisons method
+        returns -- become one BFV ciphertext [..., 2, n] per leading index
+        whose phase has LWE s's message at coefficient slots[s] (slots may
+        repeat: the messages add).  accumulate adds to `out`.  Slots other than
+        0 need the negacyclic mode to decrypt."""
+        r = self.ring
+        lwe_a, lwe_b = _as_u64(lwe_a), _as_u64(lwe_b)
+        slots = [int(s) for s in slots]
+        S, dim = len(slots), pack_key.lwe_dim
+        if any(s < 0 or s >= 1 << 32 for s in slots):
+            raise FHEError(-9, "slot index out of range")
+        if len(lwe_a.shape) < 2 or tuple(lwe_a.shape[-2:]) != (S, dim) or tuple(lwe_a.shape[:-1]) != tuple(lwe_b.shape):
+            raise FHEError(-9, "LWE masks must be [..., S, dim] and bodies [..., S]")
+        lead = tuple(lwe_b.shape[:-1])
+        if out is None:
+            if accumulate:
+                raise FHEError(-9, "accumulate needs an output to add to")
+            out = _empty(lwe_a, lead + (2, r.degree))
+        bk, ba, bb, bo = _Buf(_as_u64(pack_key.key)), _Buf(lwe_a), _Buf(lwe_b), _Buf(out, True)
+        nb = bb.count // S if S else 0
+        if bo.count != nb * 2 * r.degree or bk.count != dim * pack_key.level * 2 * r.degree:
+            raise FHEError(-9, "output must be [..., 2, n] and the key [dim level, 2, n]")
+        w = _where(bk, ba, bb, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_lwe_pack_batch(r._h, pack_key.base_log, pack_key.level, dim, bk.ptr, ba.ptr, bb.ptr,
+                                        (C.c_uint32 * max(1, S))(*slots), S, int(bool(accumulate)), bo.ptr, nb, w))
+        return out
+
 
 class BootstrapEngine:
     """The TFHE pieces of BootstrapEngine (bootstrap_engine.cpp) batched over
@@ -1946,6 +2011,12 @@ class Comparisons:
             return np.zeros(lead + (self.dim,), dtype=np.uint64), np.zeros(lead, dtype=np.uint64)
         halves = [(new, e, neg, offs) for e in existing for neg in (False, True)]
         return self._sum_signs(halves, slots, 0)
+
+    @staticmethod
+    def pack(result, slots, pack_key: "PackKey", engine: "EncryptionEngine", out=None, accumulate: bool = False):
+        """A comparison result (a, b) back as one BFV ciphertext per leading
+        index, bit s at coefficient slots[s] (EncryptionEngine.pack_lwe)."""
+        return engine.pack_lwe(result[0], result[1], slots, pack_key, out, accumulate)
 
 
 def decompose_polynomial(ring: NTTProcessor, poly, base_log: int, level: int, out=None):

@@ -34,6 +34,15 @@ export interface BootstrapKey {
   readonly keyId: bigint;
   readonly lweDimension: number;
 }
+/** The packing key-switch key of generatePackKey (the bootstrap key's LWE key under the ring key). */
+export interface PackKey {
+  readonly __brand: 'PackKey';
+  readonly handle: bigint;
+  readonly keyId: bigint;
+  readonly decompBaseLog: number;
+  readonly decompLevel: number;
+  readonly lweDimension: number;
+}
 export interface Ciphertext {
   readonly __brand: 'Ciphertext';
   readonly handle: bigint;
@@ -303,6 +312,21 @@ export interface FHECompareEngine extends FHEThresholdEngine {
   detectDuplicate(ct: Ciphertext, existing: Ciphertext[], bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
 }
 
+/** Decomposition of a pack key; the default (base 2^8, enough levels to cover the modulus) decrypts. */
+export interface PackKeyOptions {
+  decompBaseLog?: number;
+  decompLevel?: number;
+}
+
+/** LWE-to-RLWE packing (fhe_lwe_pack_batch): the encrypted bits of the comparisons, which are LWE
+ * ciphertexts under the bootstrap key's LWE key, come back as ONE BFV ciphertext with bit s at
+ * coefficient slots[s] (repeated slots add), so that the tallies, the weighted tallies and the
+ * threshold decryption apply to them.  Slots other than 0 need mode 'negacyclic' to decrypt. */
+export interface FHEPackEngine extends FHECompareEngine {
+  generatePackKey(sk: SecretKey, bk: BootstrapKey, options?: PackKeyOptions): Promise<PackKey>;
+  packBits(bits: Ciphertext[], slots: number[], packKey: PackKey): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -374,6 +398,8 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   checkThresholds(tally: Ciphertext, thresholds: bigint[], bk: BootstrapKey): Promise<Ciphertext[]>;
   checkRange(ct: Ciphertext, min: bigint, max: bigint, bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
   detectDuplicate(ct: Ciphertext, existing: Ciphertext[], bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
+  generatePackKey(sk: SecretKey, bk: BootstrapKey, options?: PackKeyOptions): Promise<PackKey>;
+  packBits(bits: Ciphertext[], slots: number[], packKey: PackKey): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension); part names another
    * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
   deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
@@ -489,6 +515,17 @@ export declare class NttContext {
    * plus bodyOffset on the body, modulo the ring modulus (fhe_lwe_sum_batch). */
   lweSum(lweA: Words, lweB: Words, terms: number, bodyOffset: bigint, outA: Words, outB: Words): Words;
   lweSumAsync(lweA: Words, lweB: Words, terms: number, bodyOffset: bigint, outA: Words, outB: Words): Promise<Words>;
+  /** out [batch][2][n] (+= with accumulate) = the packing key switch of lweA [batch][S][dim], lweB [batch][S]
+   * under packKey [dim*level][2][n], LWE s at coefficient slots[s] (fhe_lwe_pack_batch); slots is a host array. */
+  lwePack(baseLog: number, level: number, packKey: Words, lweA: Words, lweB: Words, slots: BigUint64Array,
+    accumulate: number, out: Words): Words;
+  lwePackAsync(baseLog: number, level: number, packKey: Words, lweA: Words, lweB: Words, slots: BigUint64Array,
+    accumulate: number, out: Words): Promise<Words>;
+  /** out [dim*level][2][n] = the pack key of lweSk (BigInt64Array or device words) under sk (fhe_pack_key_generate). */
+  packKeyGenerate(sk: Words, lweSk: BigInt64Array | Words, baseLog: number, level: number, seed: BigUint64Array,
+    stream: bigint | number, noiseStd: number, out: Words): Words;
+  packKeyGenerateAsync(sk: Words, lweSk: BigInt64Array | Words, baseLog: number, level: number, seed: BigUint64Array,
+    stream: bigint | number, noiseStd: number, out: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

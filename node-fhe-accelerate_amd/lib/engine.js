@@ -1192,6 +1192,58 @@ function makeEngineClass(native) {
       });
     }
 
+    // ---- LWE-to-RLWE packing (fhe_lwe_pack_batch): the comparison bits back
+    // as one BFV ciphertext, bit s at coefficient slots[s], so that the tally,
+    // the weighted tally and the threshold decryption apply to them.
+    /** The packing key of the bootstrap key's LWE key under sk (fhe_pack_key_generate):
+     *  rows (i, l) encrypt lweSk[i] 2^((level-1-l) baseLog); level * baseLog must
+     *  cover the modulus for the packed ciphertext to decrypt (the default does). */
+    async generatePackKey(sk, bk, options) {
+      this._check();
+      return guard(async () => {
+        const s = this._st(sk, 'SecretKey');
+        const b = this._st(bk, 'BootstrapKey');
+        if (sk.keyId !== bk.keyId || !s.lweDev) throw new FHEError('Bootstrap key does not match the secret key', FHEErrorCode.KEY_MISMATCH);
+        const o = options || {};
+        const bl = o.decompBaseLog || 8;
+        const bits = (this._q - 1n).toString(2).length;
+        const lv = o.decompLevel || Math.ceil(bits / bl);
+        if (bl < 1 || bl > 63 || lv < 1 || (lv - 1) * bl >= 64) throw new FHEError('invalid decomposition (baseLog, level)', FHEErrorCode.INVALID_PARAMETERS);
+        const key = this._buf(b.dim * lv * 2 * this._n);
+        await this._ctx.packKeyGenerateAsync(s.buf, s.lweDev, bl, lv, this._seed, this._streams(2), this._std, key);
+        return this._handle('PackKey', { keyId: sk.keyId, decompBaseLog: bl, decompLevel: lv, lweDimension: b.dim },
+          { buf: key, baseLog: bl, level: lv, dim: b.dim });
+      });
+    }
+    /** bits: bootstrapped LWE ciphertexts (what the comparisons return); the result
+     *  decrypts (packed) to bit s at slot slots[s]; repeated slots add their bits. */
+    async packBits(bits, slots, packKey) {
+      this._check();
+      return guard(async () => {
+        const p = this._st(packKey, 'PackKey');
+        if (!Array.isArray(bits) || bits.length === 0 || !Array.isArray(slots) || slots.length !== bits.length) {
+          throw new FHEError('bits must be a non-empty Ciphertext[] with one slot each', FHEErrorCode.INVALID_PARAMETERS);
+        }
+        const S = bits.length, dim = p.dim, n = this._n;
+        for (const h of slots) {
+          if (!Number.isInteger(h) || h < 0 || h >= n) throw new FHEError('slot index out of range', FHEErrorCode.INVALID_PARAMETERS);
+        }
+        const la = this._buf(S * dim), lb = this._buf(S);
+        bits.forEach((ct, s) => {
+          const c = this._st(ct, 'Ciphertext');
+          if (c.kind !== 'lwe' || c.dim !== dim) throw new FHEError('packBits takes bootstrapped LWE ciphertexts of the key\'s dimension', FHEErrorCode.INVALID_PARAMETERS);
+          if (ct.keyId !== packKey.keyId) throw new FHEError('Pack key does not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+          la.copyFrom(c.buf, s * dim, 0, dim);
+          lb.copyFrom(c.buf, s, dim, 1);
+        });
+        const out = this._buf(2 * n);
+        await this._ctx.lwePackAsync(p.baseLog, p.level, p.buf, la, lb, BigUint64Array.from(slots, (h) => BigInt(h)), 0, out);
+        la.free();
+        lb.free();
+        return this._ct(out, packKey.keyId, Math.min(...bits.map((c) => c.noiseBudget)) - 1, 1, { packed: true });
+      });
+    }
+
     // ---- serialisation: binary = header words + the native words, checksum = SHA-256
     _serialize(kind, h, words, meta, opts) {
       const fmt = (opts && opts.format) || 'binary';

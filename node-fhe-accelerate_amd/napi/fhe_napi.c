@@ -1677,6 +1677,38 @@ static napi_value ctx_lwe_sum(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[4], keep, 4);
 }
 
+/* lwePack(baseLog, level, packKey [dim*level][2][n], lweA [batch][S][dim], lweB [batch][S], slots (host
+ * BigUint64Array [S]), accumulate, out [batch][2][n]): the packing key switch (fhe_lwe_pack_batch) */
+static int run_lwe_pack(job *j) {
+    return fhe_lwe_pack_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], (uint32_t)j->v[2], j->p[0], j->p[1], j->p[2],
+                              (const uint32_t *)j->owned, (size_t)j->v[3], (int)j->v[4], j->p[3], j->batch, j->where);
+}
+static napi_value ctx_lwe_pack(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "lwePack(baseLog, level, packKey [dim*level*2n], lweA [batch*S*dim], lweB [batch*S], slots (BigUint64Array), "
+        "accumulate, out [batch*2n])";
+    call k;
+    if (call_begin(env, info, 8, &k)) return NULL;
+    uint64_t bl, lv, *key, *a, *b, *sl, acc, *o;
+    size_t nkey, na, nb, nsl, no;
+    if (num_arg(env, &k, 0, &bl) || num_arg(env, &k, 1, &lv) || arr_arg(env, &k, 2, &key, &nkey) ||
+        arr_arg(env, &k, 3, &a, &na) || arr_arg(env, &k, 4, &b, &nb) || k.argc < 6 ||
+        get_u64_array(env, k.argv[5], &sl, &nsl) || num_arg(env, &k, 6, &acc) || arr_arg(env, &k, 7, &o, &no) ||
+        lv == 0 || nsl == 0 || no == 0 || no % (2 * k.n) || nkey == 0 || nkey % (lv * 2 * k.n))
+        return bad_args(env, usage), NULL;
+    const size_t batch = no / (2 * k.n), dim = nkey / (lv * 2 * k.n);
+    if (nb != batch * nsl || na != nb * dim) return range_err(env, "lweA [batch][S][dim], lweB [batch][S], out [batch][2][n]");
+    for (size_t i = 0; i < nsl; ++i)
+        if (sl[i] >= k.n) return range_err(env, "slot index out of range");
+    job *j = job_new(&k, run_lwe_pack, NULL);
+    j->owned = (uint64_t *)malloc(nsl * 4 + 8);
+    for (size_t i = 0; i < nsl; ++i) ((uint32_t *)j->owned)[i] = (uint32_t)sl[i];
+    j->p[0] = key; j->p[1] = a; j->p[2] = b; j->p[3] = o;
+    j->v[0] = bl; j->v[1] = lv; j->v[2] = dim; j->v[3] = nsl; j->v[4] = acc ? 1 : 0; j->batch = batch;
+    napi_value keep[4] = {k.argv[2], k.argv[3], k.argv[4], k.argv[7]};
+    return job_go(env, &k, j, k.argv[7], keep, 4);
+}
+
 /* ---- randomness and key material (fhe_sample_batch, fhe_*_generate) ---- */
 /* sample(kind, seed, stream, noiseStd, out) */
 static int run_sample(job *j) {
@@ -1781,6 +1813,29 @@ static napi_value ctx_ksk_gen(napi_env env, napi_callback_info info) {
     j->v[1] = stream; j->v[2] = bl; j->v[3] = lv; j->v[4] = ng; j->v[5] = nl; j->d = sd; memcpy(j->v + 6, seed, 32);
     napi_value keep[4] = {k.argv[0], k.argv[1], k.argv[7], k.argv[8]};
     return job_go(env, &k, j, k.argv[8], keep, 4);
+}
+/* packKeyGenerate(sk [n], lweSk: BigInt64Array [dim], baseLog, level, seed, stream, noiseStd,
+ * out [dim L][2][n]): the key of lwePack (fhe_pack_key_generate) */
+static int run_pack_key_gen(job *j) {
+    return fhe_pack_key_generate(j->c, (uint32_t)j->v[2], (uint32_t)j->v[3], j->p[0], (const int64_t *)j->p[1],
+                                 (uint32_t)j->v[5], j->v + 6, j->v[1], j->d, j->p[2], j->where);
+}
+static napi_value ctx_pack_key_gen(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 8, &k)) return NULL;
+    uint64_t seed[4], stream, bl, lv, *sk, *ls, *o;
+    size_t ns, nl, no;
+    double sd;
+    if (arr_arg(env, &k, 0, &sk, &ns) || arr_arg(env, &k, 1, &ls, &nl) || num_arg(env, &k, 2, &bl) ||
+        num_arg(env, &k, 3, &lv) || seed_arg(env, &k, 4, seed) || num_arg(env, &k, 5, &stream) ||
+        dbl_arg(env, &k, 6, &sd) || arr_arg(env, &k, 7, &o, &no) || ns != k.n || no != nl * lv * 2 * k.n)
+        return bad_args(env, "packKeyGenerate(sk [n], lweSk (BigInt64Array), baseLog, level, seed, stream, noiseStd, "
+                             "out [dim L][2][n])"), NULL;
+    job *j = job_new(&k, run_pack_key_gen, NULL);
+    j->p[0] = sk; j->p[1] = ls; j->p[2] = o;
+    j->v[1] = stream; j->v[2] = bl; j->v[3] = lv; j->v[5] = nl; j->d = sd; memcpy(j->v + 6, seed, 32);
+    napi_value keep[3] = {k.argv[0], k.argv[1], k.argv[7]};
+    return job_go(env, &k, j, k.argv[7], keep, 3);
 }
 /* lweDecrypt(t, sk: BigInt64Array [dim], lweA [batch][dim], lweB [batch], values [batch], phase?) */
 static int run_lwe_dec(job *j) {
@@ -1923,6 +1978,8 @@ static napi_value init(napi_env env, napi_value exports) {
         M("keySwitch", ctx_key_switch),
         M("slotExtract", ctx_slot_extract),
         M("lweSum", ctx_lwe_sum),
+        M("lwePack", ctx_lwe_pack),
+        M("packKeyGenerate", ctx_pack_key_gen),
         M("sample", ctx_sample),
         M("publicKeyGenerate", ctx_pk_gen),
         M("evalKeyGenerate", ctx_ek_gen),
