@@ -229,6 +229,69 @@ int fhe_ct_multiply_relin_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level,
                                 const uint64_t *ct2, const uint64_t *rlk_ntt, uint64_t *out, size_t batch,
                                 int where);
 
+/* ---- Galois automorphisms, re-keying and the slot-isolating trace --------
+ * Key switching of a degree-1 ciphertext, with or without the automorphism
+ * X -> X^g in front of it.  (No reference counterpart: its EncryptionEngine
+ * switches only s^2 -> s.)
+ * sigma_g  for odd g, 1 <= g < 2n: for every j < n, with k = j*g mod 2n,
+ *   out[k] = in[j] mod q when k < n, else out[k - n] = (q - in[j] mod q) % q.
+ *   Input words may be any u64, outputs are canonical; g = 1 is the identity,
+ *   a copy of the reduced words.
+ * fhe_poly_galois_batch    sigma_g of npoly polynomials [npoly][n], out of
+ *   place.  Every context: any n, any odd q < 2^64, either mode (no transform
+ *   runs).  FHE_ERR_INVALID_ARG: "Galois element must be odd", "Galois element
+ *   out of range" (g >= 2n), out overlapping in, a null buffer, npoly == 0; the
+ *   parity, null and zero-count checks come before the context is looked at.
+ *   A multi-device context splits npoly.
+ * fhe_ct_galois_batch      ct [batch][2][n] = (c0, c1) -> out [batch][2][n].
+ *   With d_l = (sigma_g(c1) >> l*base_log) & (2^base_log - 1), relinearisation's
+ *   unsigned LSB-first digit of the canonical word, and swk_ntt [level][2][n]
+ *   the prepared pairs (a_l, b_l) of fhe_switch_key_generate:
+ *     out0 = sigma_g(c0) [+ c0 mod q] + sum_l d_l (*) b_l
+ *     out1 =             [  c1 mod q] + sum_l d_l (*) a_l
+ *   the bracketed terms present when add_input != 0 (the trace step ct +
+ *   sigma_g(ct) in one launch).  Word-identical to the chain
+ *   fhe_poly_galois_batch on both components, fhe_poly_add_batch when
+ *   add_input, and fhe_relinearize_batch on ct3 = (sigma_g(c0) [+ c0],
+ *   [c1 mod q | 0], sigma_g(c1)); level 0 therefore copies rows 0 and 1 of that
+ *   ct3.  Coefficient form only.  Every context: one fused kernel for n <=
+ *   16384 and q < 2^62, otherwise the permutation kernel into a bounded
+ *   stream-ordered temporary and the composed relinearisation.  (base_log,
+ *   level) as fhe_relinearize_batch.  FHE_ERR_INVALID_ARG: the g errors above,
+ *   a null ct or out (or key with level > 0), batch == 0, out overlapping ct;
+ *   all but the range and overlap checks come before the context is looked
+ *   at.  A multi-device context splits the batch; FHE_HOST stages every
+ *   buffer, the key included.
+ * fhe_ct_trace_batch       the partial field trace: swk_ntt
+ *   [steps][level][2][n], block i the prepared Galois key of g_i = n / 2^i + 1
+ *   (g_0 = n + 1 negates the odd coefficients; the last of a full trace is
+ *   g = 3); 1 <= steps <= log2(n).  Words: x = fhe_poly_mul_scalar_batch(ct,
+ *   (2^steps)^-1 mod q), then x <- fhe_ct_galois_batch(g_i, key_i, x,
+ *   add_input = 1) for i = 0 .. steps-1, bit-identical to that chain; the
+ *   steps ping-pong between out and one stream-ordered temporary without a
+ *   host synchronisation.  In negacyclic mode the coefficients of the phase at
+ *   multiples of 2^steps come back exactly (message and input noise; the
+ *   pre-multiplication is mod q, not mod t, so t may be even) and every other
+ *   coefficient becomes 0 plus key-switch noise; after steps = log2(n) only
+ *   coefficient 0 survives.
+ * Meaning and modes: the words are defined in both modes.  For g != 1 the
+ *   result decrypts to sigma_g of the message only under FHE_MODE_NEGACYCLIC:
+ *   the compat transform product does not commute with sigma_g, exactly as
+ *   packed slots other than 0.  For g = 1 (re-keying) the message moves to
+ *   sk_to in both modes (only the bilinearity and associativity of the
+ *   context's product (*) are used), but the key-switch noise sum_l d_l (*) e_l
+ *   is small only under the true ring product: the compat product of two small
+ *   polynomials is not small once their degrees add up to n or more.  A
+ *   re-keyed ciphertext therefore decrypts under sk_to in compat mode only
+ *   with key errors confined to coefficient 0 (constants multiply as scalars),
+ *   and with real keys only under FHE_MODE_NEGACYCLIC; the exact-integer model
+ *   of tests/test_galois_abi.py shows both. */
+int fhe_poly_galois_batch(fhe_ctx *ctx, uint32_t g, const uint64_t *in, uint64_t *out, size_t npoly, int where);
+int fhe_ct_galois_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, uint32_t g, const uint64_t *swk_ntt,
+                        const uint64_t *ct, int add_input, uint64_t *out, size_t batch, int where);
+int fhe_ct_trace_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, uint32_t steps, const uint64_t *swk_ntt,
+                       const uint64_t *ct, uint64_t *out, size_t batch, int where);
+
 /* ---- ciphertext squaring and anomaly score (encryption.cpp:1004-1055, 1305-1321)
  * EncryptionEngine::square / square_relin and compute_anomaly_score's
  * relinearize(square(subtract(ballot, expected))).  The words equal
@@ -657,6 +720,22 @@ int fhe_bootstrap_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t le
  *   a_l uniform (stream + 2l), e_l error (stream + 2l + 1),
  *   b_l = a_l (*) s + e_l + (s (*) s) * power_l, power_0 = 1,
  *   power_{l+1} = (power_l * 2^base_log) % q in u64 arithmetic (as the reference).
+ * fhe_switch_key_generate     the key of fhe_ct_galois_batch and
+ *   fhe_ct_trace_batch: swk [level][2][n] = (a_l, b_l) in the layout, with the
+ *   draws (a_l uniform on stream + 2l, e_l Gaussian on stream + 2l + 1) and the
+ *   u64 power update of fhe_eval_key_generate;
+ *   b_l = a_l (*) sk_to + e_l + m * power_l, m[j] = (q - sigma_g(sk_from)[j]) % q:
+ *   the NEGATED source key, so that the unsigned digits of sigma_g(c1) give the
+ *   phase c0 - c1 (*) s without negating c1.  The words equal fhe_sample_batch
+ *   twice, fhe_polymul_batch against sk_to, fhe_poly_add_batch,
+ *   fhe_poly_galois_batch + fhe_poly_neg_batch on sk_from,
+ *   fhe_poly_mul_scalar_batch by power_l % q and fhe_poly_add_batch, bit for
+ *   bit.  sk_from == sk_to with g != 1 is a Galois key; g = 1 with two
+ *   different keys is a re-keying key.  It is prepared with
+ *   fhe_relin_key_prepare (same shape, same opaque form).  Errors as
+ *   fhe_eval_key_generate, plus "Galois element must be odd" (before the
+ *   context is looked at), "Galois element out of range" and swk overlapping
+ *   either key; level == 0 returns FHE_OK and writes nothing.
  * fhe_ggsw_encrypt_batch      encrypt_ggsw (bootstrap_engine.cpp:268-306) of
  *   count values (the LWE key of a bootstrapping key, :308-360): out
  *   [count][(k+1)*level][k+1][n] coefficient form, row (row, l) an
@@ -706,6 +785,9 @@ int fhe_public_key_generate(fhe_ctx *ctx, const uint64_t *sk, const uint64_t see
                             uint64_t *pk, int where);
 int fhe_eval_key_generate(fhe_ctx *ctx, const uint64_t *sk, uint32_t base_log, uint32_t level, const uint64_t seed[4],
                           uint64_t stream, double std_dev, uint64_t *rlk, int where);
+int fhe_switch_key_generate(fhe_ctx *ctx, const uint64_t *sk_to, const uint64_t *sk_from, uint32_t g, uint32_t base_log,
+                            uint32_t level, const uint64_t seed[4], uint64_t stream, double std_dev, uint64_t *swk,
+                            int where);
 int fhe_ggsw_encrypt_batch(fhe_ctx *ctx, uint32_t k, uint32_t base_log, uint32_t level, const int64_t *values,
                            size_t count, const uint64_t *sk, const uint64_t seed[4], uint64_t stream, double std_dev,
                            uint64_t *out, int where);

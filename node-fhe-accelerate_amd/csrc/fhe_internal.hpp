@@ -86,6 +86,12 @@ hipError_t launch_extprod_acc(const Plan &p, int level, int base_log, const uint
 // rlk [level][2][n] (a_l, b_l) in NTT-Montgomery form -> out [batch][2][n].
 hipError_t launch_relin(const Plan &p, int level, int base_log, const uint64_t *ct3, const uint64_t *rlk,
                         uint64_t *out, size_t batch);
+// Galois key switch of degree-1 ciphertexts (fhe_ct_galois_batch; k_dmac
+// MODE 4): ct [batch][2][n], swk [level][2][n] (a_l, b_l) in NTT-Montgomery
+// form, ginv = g^-1 mod 2n -> out [batch][2][n]; level >= 1, the fused family
+// only (n <= 16384, q < 2^62).
+hipError_t launch_ct_galois(const Plan &p, int level, int base_log, uint32_t ginv, int add_input, const uint64_t *ct,
+                            const uint64_t *swk, uint64_t *out, size_t batch);
 // One blind-rotation CMux step over a batch of GLWE accumulators (ping-pong
 // buffers acc_in -> acc_out); step = LWE mask index i, bsk[i] = ggsw.
 hipError_t launch_cmux_rotate(const Plan &p, int k1, int level, int base_log, const uint64_t *acc_in,
@@ -175,6 +181,11 @@ hipError_t launch_modmul(const ModConsts &m, const uint64_t *a, const uint64_t *
 hipError_t launch_addsub(const ModConsts &m, const uint64_t *a, const uint64_t *b, uint64_t *c, size_t n, int sub,
                          hipStream_t s);
 hipError_t launch_neg(uint64_t q, const uint64_t *a, uint64_t *c, size_t n, hipStream_t s);
+// sigma_g of npoly rows (galois.hip): out + i out_pitch = sigma_g(in + i
+// in_pitch) (+ add + i in_pitch, mod q, when add != nullptr); ginv = g^-1 mod
+// 2n, n = 2^logn >= 4, pitches in words (even), 16-byte aligned rows.
+hipError_t launch_poly_galois(const ModConsts &m, uint32_t logn, uint32_t ginv, const uint64_t *in, const uint64_t *add,
+                              uint64_t *out, size_t npoly, size_t in_pitch, size_t out_pitch, hipStream_t s);
 // RNS ring: pointwise product (op 0), add (1), sub (2) over [limbs][per] with
 // per-limb constants tab[limb] (device array), one launch.
 hipError_t launch_ew_limbs(const ModConsts *tab, int limbs, const uint64_t *a, const uint64_t *b, uint64_t *c,

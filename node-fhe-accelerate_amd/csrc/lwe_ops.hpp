@@ -36,5 +36,14 @@ __device__ __forceinline__ uint64_t rotated_at(const uint64_t *c, uint32_t p, ui
     if (j < n) return c[j];
     return red_q(q - c[j - n], q, mu);
 }
+// Coefficient p of sigma_g(c), the automorphism X -> X^g (g odd) of a
+// negacyclic row, for ginv = g^-1 mod 2N: c[p ginv mod 2N] reduced, with the
+// sign flip of X^N = -1.  Canonical for any raw word.
+__device__ __forceinline__ uint64_t galois_at(const uint64_t *c, uint32_t p, uint32_t ginv, uint32_t n, uint64_t q,
+                                              uint64_t mu) {
+    const uint32_t j = (p * ginv) & (2 * n - 1);
+    const uint64_t x = red_q(c[j & (n - 1)], q, mu);
+    return (j < n || x == 0) ? x : q - x;
+}
 
 }  // namespace FHE_NS

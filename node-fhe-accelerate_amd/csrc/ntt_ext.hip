@@ -23,6 +23,19 @@
 //         The rotation and the subtraction are folded into the digit load.
 // MODE 3  CMux with explicit inputs (cmux :520-540): out = ct0 +
 //         ExtProd(ct1 - ct0, ggsw).
+// MODE 4  Galois key switch of a degree-1 ciphertext (fhe_ct_galois_batch):
+//         MODE 1 with the digits taken from sigma_g(c1) instead of c2 and the
+//         addends sigma_g(c0) (+ c0) and (c1 | 0) instead of c0, c1.  No
+//         sigma_g(c) row is ever stored: coefficient p of sigma_g(c) is
+//         +-c[p g^-1 mod 2N] (lwe_ops.hpp galois_at), gathered straight from
+//         the ciphertext's own rows on the digit load and in the store
+//         epilogue.  Every word of a row is read once per pass by the one
+//         workgroup that owns the ciphertext, so HBM traffic is that of a
+//         coalesced read; what the gather costs is cache-line fan-out between
+//         L2 and the CU: g = 3 (a line per lane) measures 0.9-2.3 % over
+//         g = N + 1 (coalesced), DESIGN.md section 5.  That is all a coalesced
+//         load scattered through the transform LDS region, the alternative,
+//         could win back before paying for its barrier; it was not built.
 //
 // Every intermediate is a canonical residue and the inverse transform is
 // linear over Z_q, so  sum_r inv(X_r) == inv(sum_r X_r)  bit-exactly: keys are
@@ -66,7 +79,7 @@ constexpr int ext_stash() {
     // relinearisation (MODE 1): accumulator 0 in LDS, accumulator 1 and the
     // c2 words in VGPRs (one workgroup per CU); c2 is then read once instead
     // of once per digit level
-    if (MODE == 1 && K1 == 2 && G::P == 1 && (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024)
+    if ((MODE == 1 || MODE == 4) && K1 == 2 && G::P == 1 && (G::LW + G::N) * (int)sizeof(W) <= 160 * 1024)
         return 3;
     return 2;
 }
@@ -83,7 +96,7 @@ constexpr int ext_occ() {
 }
 
 struct DmArgs {
-    const uint64_t *src;    // MODE 0: glwe [batch][K1][N]; 1: ct [batch][3][N]; 2: acc [batch][K1][N]
+    const uint64_t *src;    // MODE 0: glwe [batch][K1][N]; 1: ct [batch][3][N]; 2: acc [batch][K1][N]; 4: ct [batch][2][N]
     const uint64_t *key;    // prepared key rows (NTT x R): 0/2: [K1*L][K1][N]; 1: [L][2][N] (a_l, b_l)
     uint64_t *out;          // [batch][K1][N]
     size_t batch;
@@ -92,6 +105,8 @@ struct DmArgs {
     uint64_t lwe_q;
     uint32_t lwe_dim, step;
     const uint64_t *src2;   // MODE 3: ct1 [batch][K1][N] (src = ct0)
+    uint32_t ginv;          // MODE 4: g^-1 mod 2N
+    int add_input;          // MODE 4: out += ct
 };
 
 // Relinearisation with 32-bit words loads the row's whole key (low words of
@@ -104,7 +119,8 @@ __global__ void __launch_bounds__(Geo<LOGN>::THREADS, (ext_occ<LOGN, W, K1, MODE
 k_dmac(DmArgs D, NttArgs<W> A) {
     using G = Geo<LOGN>;
     constexpr int STASH = ext_stash<LOGN, W, K1, MODE>();
-    constexpr bool KPF = MODE == 1 && STASH == 3 && sizeof(W) == 4;
+    constexpr bool RELIN = MODE == 1 || MODE == 4;  // unsigned LSB-first digits of one row, (a_l, b_l) keys
+    constexpr bool KPF = RELIN && STASH == 3 && sizeof(W) == 4;
     constexpr int NIN = MODE == 1 ? 3 : K1;  // source polynomials per ciphertext
     __shared__ W lds_all[G::P * G::LW + ext_extra_words<LOGN, W, K1, MODE>()];
     const uint32_t tau = threadIdx.x & (G::T - 1), pl = wg_poly<G>();
@@ -122,15 +138,19 @@ k_dmac(DmArgs D, NttArgs<W> A) {
         else return reinterpret_cast<W *>(orow + (size_t)j * G::N);
     };
     W racc[STASH == 3 ? G::E : 1];
-    uint64_t craw[STASH == 3 ? G::E : 1];  // c2 words at this lane's pass-0 positions
-    if constexpr (STASH == 3) {
-#pragma unroll
-        for (int t = 0; t < G::E; ++t) craw[t] = valid ? srow[2 * G::N + tau + cbrv(t, G::LOGE) * G::T] : 0;
-    }
+    uint64_t craw[STASH == 3 ? G::E : 1];  // c2 (MODE 4: sigma_g(c1)) words at this lane's pass-0 positions
 
     const int level = D.level;
     const uint64_t base = 1ull << D.base_log, mask = base - 1, half = base / 2;
     const uint64_t q = A.q64, mu = A.mu64, lim = (uint64_t)A.ar.q2 * 2;
+    if constexpr (STASH == 3) {
+#pragma unroll
+        for (int t = 0; t < G::E; ++t) {
+            const uint32_t p = tau + cbrv(t, G::LOGE) * G::T;
+            if constexpr (MODE == 4) craw[t] = valid ? galois_at(srow + G::N, p, D.ginv, G::N, q, mu) : 0;
+            else craw[t] = valid ? srow[2 * G::N + p] : 0;
+        }
+    }
     bool skip = false;   // MODE 2, rot == 0: output = input accumulator
     uint32_t rot = 0;
     if constexpr (MODE == 2) {
@@ -142,14 +162,14 @@ k_dmac(DmArgs D, NttArgs<W> A) {
             return;
         }
     }
-    const int rows = MODE == 1 ? level : K1 * level;
+    const int rows = RELIN ? level : K1 * level;
     for (int r = 0; r < rows; ++r) {
         // opaque per-row copy of the lane index: keeps the (loop-invariant)
         // address arithmetic inside the loop instead of 100+ hoisted VGPRs
         uint32_t tr = tau;
         asm volatile("" : "+v"(tr));
-        const int i = MODE == 1 ? 2 : r / level, l = MODE == 1 ? r : r % level;
-        const uint32_t shift = MODE == 1 ? uint32_t(l) * uint32_t(D.base_log)
+        const int i = MODE == 1 ? 2 : MODE == 4 ? 1 : r / level, l = RELIN ? r : r % level;
+        const uint32_t shift = RELIN ? uint32_t(l) * uint32_t(D.base_log)
                                          : uint32_t(level - 1 - l) * uint32_t(D.base_log);
         const uint64_t *src = srow + (size_t)i * G::N;
         const uint64_t *src2 = MODE == 3 ? D.src2 + ((valid ? poly : 0) * K1 + i) * G::N : nullptr;
@@ -164,9 +184,10 @@ k_dmac(DmArgs D, NttArgs<W> A) {
             if constexpr (STASH == 3) c = craw[STASH == 3 ? t : 0];
             else if constexpr (MODE == 2) c = subq(red_q(rotated_at(src, p, rot, G::N, q, mu), q, mu), red_q(src[p], q, mu), q);
             else if constexpr (MODE == 3) c = subq(red_q(src2[p], q, mu), red_q(src[p], q, mu), q);
+            else if constexpr (MODE == 4) c = galois_at(src, p, D.ginv, G::N, q, mu);
             else c = src[p];
             uint64_t d = (c >> shift) & mask;
-            if constexpr (MODE != 1) {
+            if constexpr (!RELIN) {
                 if (d > half) d = red_q(q - (base - d), q, mu);
             }
             return d;
@@ -208,7 +229,7 @@ k_dmac(DmArgs D, NttArgs<W> A) {
 #pragma unroll
                 for (int j = 0; j < K1; ++j) {
                     const uint32_t gi = gidx<LOGN, G::NP - 1>(tr, c0 + e);
-                    const int kj = MODE == 1 ? 1 - j : j;  // relin: c0' uses b_l, c1' uses a_l
+                    const int kj = RELIN ? 1 - j : j;  // relin: c0' uses b_l, c1' uses a_l
                     kv[e][j] = g[(size_t)kj * G::N + gi];
                     if (STASH == 3 && j > 0) pv[e][j] = r == 0 ? W(0) : racc[STASH == 3 ? c0 + e : 0];
                     else pv[e][j] = r == 0 ? W(0) : acc(j)[gi];
@@ -240,11 +261,17 @@ k_dmac(DmArgs D, NttArgs<W> A) {
             if (G::NP > 1) __syncthreads();  // every stash read of row j precedes its final stores
         }
         // MODE 1: + c_j (mod_add of encryption.cpp:953/958); MODE 2: + acc_j
-        // (cmux's add_glwe_inplace, :537), or acc_j itself when skipped.
+        // (cmux's add_glwe_inplace, :537), or acc_j itself when skipped;
+        // MODE 4: row 0 + sigma_g(c0) (+ c0), row 1 (+ c1).
         const uint64_t *addend = srow + (size_t)j * G::N;
         auto fin = [&](uint32_t gi, uint64_t x) -> uint64_t {
             if constexpr (MODE == 0) return x;
-            else {
+            else if constexpr (MODE == 4) {
+                if (!valid) return 0;
+                uint64_t a = D.add_input ? red_q(addend[gi], q, mu) : 0;
+                if (j == 0) a = addq(galois_at(srow, gi, D.ginv, G::N, q, mu), a, q);
+                return addq(x, a, q);
+            } else {
                 if (!valid) return 0;
                 const uint64_t a = addend[gi];
                 if (MODE == 2 && skip) return a;
@@ -391,6 +418,12 @@ hipError_t launch_relin(const Plan &p, int level, int base_log, const uint64_t *
                         uint64_t *out, size_t batch) {
     DmArgs D{ct3, rlk, out, batch, level, base_log, nullptr, 0, 0, 0, nullptr};
     return dmac<1>(p, 2, D);
+}
+
+hipError_t launch_ct_galois(const Plan &p, int level, int base_log, uint32_t ginv, int add_input, const uint64_t *ct,
+                            const uint64_t *swk, uint64_t *out, size_t batch) {
+    DmArgs D{ct, swk, out, batch, level, base_log, nullptr, 0, 0, 0, nullptr, ginv, add_input};
+    return dmac<4>(p, 2, D);
 }
 
 hipError_t launch_cmux_rotate(const Plan &p, int k1, int level, int base_log, const uint64_t *acc_in,

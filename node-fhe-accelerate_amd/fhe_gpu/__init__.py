@@ -139,6 +139,12 @@ SIGNATURES = [
     ("fhe_relinearize_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_ct_multiply_relin_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_poly_galois_batch", C.c_int, [vp, C.c_uint32, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_switch_key_generate", C.c_int,
+     [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_double, vp, C.c_int]),
+    ("fhe_ct_galois_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_trace_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_ct_square_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]),
     ("fhe_ct_square_relin_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
@@ -595,6 +601,19 @@ class PolynomialRing(NTTProcessor):
     def negate(self, a, out=None):
         return self._unary(lib().fhe_poly_neg_batch, a, out)
 
+    def galois(self, p, g: int, out=None):
+        """sigma_g, the automorphism X -> X^g (g odd, below 2n) of [..., n]
+        polynomials (fhe_poly_galois_batch): a signed permutation, canonical
+        output, out of place."""
+        p = _as_u64(p)
+        nb = self._batch(p)
+        out = _like(p) if out is None else out
+        bi, bo = _Buf(p), _Buf(out, True)
+        w = _where(bi, bo)
+        self._bind_stream(w)
+        _check(lib().fhe_poly_galois_batch(self._h, int(g), bi.ptr, bo.ptr, nb, w))
+        return out
+
     def multiply_scalar(self, a, scalar: int, out=None):
         a = _as_u64(a)
         nb = self._batch(a)
@@ -817,6 +836,34 @@ class EvaluationKey:
             _check(lib().fhe_relin_key_prepare(ring._h, self.level, bi.ptr, bo.ptr, w))
 
 
+class SwitchKey:
+    """Key-switching key(s) of fhe_ct_galois_batch / fhe_ct_trace_batch
+    (KeyGenerator.switch_key, KeyGenerator.galois_keys): the raw (a_l, b_l)
+    pairs ``key`` [level, 2, n] (or [steps, level, 2, n], key i for
+    ``g[i]``), the decomposition, the Galois element(s) ``g`` and the
+    NTT-domain form ``key_ntt``, prepared on first use."""
+
+    def __init__(self, ring: "PolynomialRing", key, base_log: int, level: int, g=1):
+        key = _as_u64(key)
+        if tuple(key.shape[-3:]) != (level, 2, ring.degree) or len(key.shape) not in (3, 4):
+            raise FHEError(-9, "switch key must have shape [level, 2, n] or [steps, level, 2, n]")
+        self.ring, self.key, self.base_log, self.level, self.g = ring, key, int(base_log), int(level), g
+        self.steps = int(key.shape[0]) if len(key.shape) == 4 else None
+        self._ntt = None
+
+    @property
+    def key_ntt(self):
+        if self._ntt is None:
+            out = _like(self.key)
+            if self.level:
+                bi, bo = _Buf(self.key), _Buf(out, True)
+                w = _where(bi, bo)
+                self.ring._bind_stream(w)
+                _check(lib().fhe_relin_key_prepare(self.ring._h, self.level * (self.steps or 1), bi.ptr, bo.ptr, w))
+            self._ntt = out
+        return self._ntt
+
+
 class SecretKey:
     """SecretKey (key_manager.h): the polynomial s [n] and its NTT-domain
     form prepared once on the GPU (fhe_secret_key_prepare: s and s^2)."""
@@ -995,6 +1042,39 @@ class KeyGenerator:
         _check(lib().fhe_eval_key_generate(r._h, bs.ptr, base_log, level, _seed_arr(self.seed), stream,
                                            self.noise_std, bo.ptr, w))
         return out
+
+    def switch_key(self, sk_to, sk_from, base_log: int, level: int, stream: int, g: int = 1, out=None):
+        """fhe_switch_key_generate -> SwitchKey over [level, 2, n]: switches
+        sigma_g(ct) from sigma_g(sk_from) to sk_to.  g = 1 with two keys is a
+        re-keying key, sk_from = sk_to with g != 1 a Galois key.  Streams
+        stream .. stream + 2 level - 1."""
+        r = self.ring
+        st = _as_u64(sk_to.poly if isinstance(sk_to, SecretKey) else sk_to)
+        sf = _as_u64(sk_from.poly if isinstance(sk_from, SecretKey) else sk_from)
+        out = _empty(st, (level, 2, r.degree)) if out is None else out
+        bt, bf, bo = _Buf(st), _Buf(sf), _Buf(out, True)
+        if bo.count != level * 2 * r.degree:
+            raise FHEError(-9, "switch key must be [level, 2, n]")
+        w = _where(bt, bf, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_switch_key_generate(r._h, bt.ptr, bf.ptr, int(g), base_log, level, _seed_arr(self.seed),
+                                             stream, self.noise_std, bo.ptr, w))
+        return SwitchKey(r, out, base_log, level, int(g))
+
+    def galois_keys(self, sk, base_log: int, level: int, stream: int, steps=None):
+        """The Galois keys of the trace in one buffer [steps, level, 2, n]:
+        key i for g_i = n / 2^i + 1 on streams stream + 2 level i ...;
+        steps defaults to log2(n), the full trace."""
+        r = self.ring
+        steps = r.degree.bit_length() - 1 if steps is None else int(steps)
+        if steps < 1 or steps > r.degree.bit_length() - 1:
+            raise FHEError(-9, "steps must be between 1 and log2(n)")
+        s = _as_u64(sk.poly if isinstance(sk, SecretKey) else sk)
+        out = _empty(s, (steps, level, 2, r.degree))
+        gs = [(r.degree >> i) + 1 for i in range(steps)]
+        for i, g in enumerate(gs):
+            self.switch_key(s, s, base_log, level, stream + 2 * level * i, g, out=out[i])
+        return SwitchKey(r, out, base_log, level, gs)
 
     def threshold_keys(self, threshold: int, total_shares: int, stream: int, device_out: bool = False):
         """generate_threshold_keys (:479-546): a ternary master key from
@@ -1681,6 +1761,70 @@ class EncryptionEngine:
         _check(lib().fhe_lwe_pack_batch(r._h, pack_key.base_log, pack_key.level, dim, bk.ptr, ba.ptr, bb.ptr,
                                         (C.c_uint32 * max(1, S))(*slots), S, int(bool(accumulate)), bo.ptr, nb, w))
         return out
+
+
+    def apply_galois(self, ct, key: "SwitchKey", add_input: bool = False, out=None):
+        """fhe_ct_galois_batch: [..., 2, n] -> the encryption under the key's
+        target of sigma_g of the message (g = key.g), plus ct itself with
+        add_input.  g != 1 needs the negacyclic mode to decrypt."""
+        r = self.ring
+        if key.steps is not None:
+            raise FHEError(-9, "apply_galois takes one key [level, 2, n]")
+        ct = _as_u64(ct)
+        nb = _lead(ct, (2, r.degree))
+        out = _like(ct) if out is None else out
+        bi, bo = _Buf(ct), _Buf(out, True)
+        bk = _Buf(key.key_ntt) if key.level else None
+        w = _where(bi, bk, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_galois_batch(r._h, key.base_log, key.level, int(key.g), bk.ptr if bk else None, bi.ptr,
+                                         int(bool(add_input)), bo.ptr, nb, w))
+        return out
+
+    def rekey(self, ct, key: "SwitchKey", out=None):
+        """Hands a ciphertext to another secret key without decrypting it: a
+        key switch with a re-keying key (KeyGenerator.switch_key with g = 1)."""
+        if key.steps is not None or key.g != 1:
+            raise FHEError(-9, "rekey needs a key with g = 1")
+        return self.apply_galois(ct, key, False, out)
+
+    def trace(self, ct, keys: "SwitchKey", steps=None, out=None):
+        """fhe_ct_trace_batch: after `steps` automorphism steps (default: all
+        of keys) only the coefficients of the phase at multiples of 2^steps
+        remain, exactly; the rest become key-switch noise around 0."""
+        r = self.ring
+        if keys.steps is None:
+            raise FHEError(-9, "trace needs the keys of KeyGenerator.galois_keys [steps, level, 2, n]")
+        steps = keys.steps if steps is None else int(steps)
+        if steps < 1 or steps > keys.steps:
+            raise FHEError(-9, "steps must be between 1 and the number of keys")
+        ct = _as_u64(ct)
+        nb = _lead(ct, (2, r.degree))
+        out = _like(ct) if out is None else out
+        bi, bo = _Buf(ct), _Buf(out, True)
+        bk = _Buf(keys.key_ntt) if keys.level else None
+        w = _where(bi, bk, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_trace_batch(r._h, keys.base_log, keys.level, steps, bk.ptr if bk else None, bi.ptr,
+                                        bo.ptr, nb, w))
+        return out
+
+    def isolate_slot(self, ct, slot: int, keys: "SwitchKey", out=None):
+        """Zeroes every coefficient of the message but `slot`: rotate by
+        X^-slot, the full trace, rotate back by X^+slot.  Needs the log2(n)
+        keys of KeyGenerator.galois_keys and the negacyclic mode."""
+        r = self.ring
+        if keys.steps != r.degree.bit_length() - 1:
+            raise FHEError(-9, "isolate_slot needs the log2(n) keys of the full trace")
+        slot = int(slot)
+        if slot < 0 or slot >= r.degree:
+            raise FHEError(-9, "slot index out of range")
+        ct = _as_u64(ct)
+        nb = _lead(ct, (2, r.degree))
+        rot = BootstrapEngine(r, keys.base_log, max(1, keys.level))
+        x = rot.multiply_glwe_by_monomial(ct, [-slot] * nb)
+        y = self.trace(x, keys)
+        return rot.multiply_glwe_by_monomial(y, [slot] * nb, out=x if out is None else out)
 
 
 class BootstrapEngine:

@@ -327,6 +327,44 @@ export interface FHEPackEngine extends FHECompareEngine {
   packBits(bits: Ciphertext[], slots: number[], packKey: PackKey): Promise<Ciphertext>;
 }
 
+/** A key-switching key of generateSwitchKey: hands sigma_g of a ciphertext of `fromKeyId` to `keyId`. */
+export interface SwitchKey {
+  readonly __brand: 'SwitchKey';
+  readonly handle: bigint;
+  readonly keyId: bigint;
+  readonly fromKeyId: bigint;
+  readonly galoisElement: number;
+  readonly decompBaseLog: number;
+  readonly decompLevel: number;
+}
+/** The Galois keys g_i = n / 2^i + 1 of `steps` trace steps (generateGaloisKeys). */
+export interface GaloisKeys {
+  readonly __brand: 'GaloisKeys';
+  readonly handle: bigint;
+  readonly keyId: bigint;
+  readonly steps: number;
+  readonly decompBaseLog: number;
+  readonly decompLevel: number;
+}
+/** Decomposition and Galois element of a switch key; the default (g = 1, base 2^8, enough levels
+ * to cover the modulus) re-keys and decrypts. */
+export interface SwitchKeyOptions {
+  galoisElement?: number;
+  decompBaseLog?: number;
+  decompLevel?: number;
+}
+
+/** Key switching of degree-1 ciphertexts (fhe_ct_galois_batch, fhe_ct_trace_batch): re-keying
+ * without decrypting, the automorphisms X -> X^g, and the trace that opens one slot of a packed
+ * ciphertext and nothing else.  g != 1 and isolateSlot need mode 'negacyclic' to decrypt. */
+export interface FHEGaloisEngine extends FHEPackEngine {
+  generateSwitchKey(skTo: SecretKey, skFrom: SecretKey, options?: SwitchKeyOptions): Promise<SwitchKey>;
+  generateGaloisKeys(sk: SecretKey, steps?: number, options?: PackKeyOptions): Promise<GaloisKeys>;
+  applyGalois(ct: Ciphertext, g: number, key: SwitchKey): Promise<Ciphertext>;
+  reKey(ct: Ciphertext, key: SwitchKey): Promise<Ciphertext>;
+  isolateSlot(ct: Ciphertext, slot: number, keys: GaloisKeys): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -400,6 +438,11 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   detectDuplicate(ct: Ciphertext, existing: Ciphertext[], bk: BootstrapKey, options?: CompareOptions): Promise<Ciphertext>;
   generatePackKey(sk: SecretKey, bk: BootstrapKey, options?: PackKeyOptions): Promise<PackKey>;
   packBits(bits: Ciphertext[], slots: number[], packKey: PackKey): Promise<Ciphertext>;
+  generateSwitchKey(skTo: SecretKey, skFrom: SecretKey, options?: SwitchKeyOptions): Promise<SwitchKey>;
+  generateGaloisKeys(sk: SecretKey, steps?: number, options?: PackKeyOptions): Promise<GaloisKeys>;
+  applyGalois(ct: Ciphertext, g: number, key: SwitchKey): Promise<Ciphertext>;
+  reKey(ct: Ciphertext, key: SwitchKey): Promise<Ciphertext>;
+  isolateSlot(ct: Ciphertext, slot: number, keys: GaloisKeys): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension); part names another
    * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
   deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
@@ -526,6 +569,23 @@ export declare class NttContext {
     stream: bigint | number, noiseStd: number, out: Words): Words;
   packKeyGenerateAsync(sk: Words, lweSk: BigInt64Array | Words, baseLog: number, level: number, seed: BigUint64Array,
     stream: bigint | number, noiseStd: number, out: Words): Promise<Words>;
+  /** out [batch][n] = sigma_g(a), the automorphism X -> X^g (odd g < 2n) as a signed permutation (fhe_poly_galois_batch). */
+  polyGalois(a: Words, g: number, out: Words): Words;
+  polyGaloisAsync(a: Words, g: number, out: Words): Promise<Words>;
+  /** out [level][2][n] = the key that switches sigma_g(ct) from sigma_g(skFrom) to skTo (fhe_switch_key_generate);
+   * prepared with prepareRelinKey. */
+  switchKeyGenerate(skTo: Words, skFrom: Words, g: number, baseLog: number, level: number, seed: BigUint64Array,
+    stream: bigint | number, noiseStd: number, out: Words): Words;
+  switchKeyGenerateAsync(skTo: Words, skFrom: Words, g: number, baseLog: number, level: number, seed: BigUint64Array,
+    stream: bigint | number, noiseStd: number, out: Words): Promise<Words>;
+  /** out [batch][2][n] = the key switch of sigma_g(ct) (+ ct with addInput) under swkPrep [level][2][n]
+   * (fhe_ct_galois_batch). */
+  ctGalois(baseLog: number, g: number, swkPrep: Words, ct: Words, addInput: number, out: Words): Words;
+  ctGaloisAsync(baseLog: number, g: number, swkPrep: Words, ct: Words, addInput: number, out: Words): Promise<Words>;
+  /** out [batch][2][n] = `steps` steps of the field trace under keysPrep [steps][level][2][n], key i for
+   * g_i = n / 2^i + 1 (fhe_ct_trace_batch). */
+  ctTrace(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Words;
+  ctTraceAsync(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

@@ -1244,6 +1244,109 @@ function makeEngineClass(native) {
       });
     }
 
+    // ---- Galois automorphisms, re-keying and the slot-isolating trace
+    // (fhe_switch_key_generate, fhe_ct_galois_batch, fhe_ct_trace_batch).
+    _switchDecomp(options) {
+      const o = options || {};
+      const bl = o.decompBaseLog || 8;
+      const lv = o.decompLevel || Math.ceil((this._q - 1n).toString(2).length / bl);
+      if (bl < 1 || bl > 63 || lv < 1 || (lv - 1) * bl >= 64) throw new FHEError('invalid decomposition (baseLog, level)', FHEErrorCode.INVALID_PARAMETERS);
+      return { bl, lv };
+    }
+    /** raw pairs (a_l, b_l) into `raw`, one key of 2 * lv streams */
+    async _switchKeyInto(to, from, g, bl, lv, raw) {
+      await this._ctx.switchKeyGenerateAsync(to.buf, from.buf, g, bl, lv, this._seed, this._streams(2 * lv), this._std, raw);
+    }
+    /** The key that hands ciphertexts of skFrom to skTo; options.galoisElement g (odd,
+     *  below 2n; default 1) makes it the key of applyGalois(ct, g, key).  skFrom = skTo
+     *  with g != 1 is a Galois key, g = 1 with two keys a re-keying key. */
+    async generateSwitchKey(skTo, skFrom, options) {
+      this._check();
+      return guard(async () => {
+        const to = this._st(skTo, 'SecretKey'), from = this._st(skFrom, 'SecretKey');
+        const g = (options && options.galoisElement) || 1;
+        if (!Number.isInteger(g) || g < 1 || g >= 2 * this._n || g % 2 === 0) throw new FHEError('Galois element must be odd and below 2n', FHEErrorCode.INVALID_PARAMETERS);
+        const { bl, lv } = this._switchDecomp(options);
+        const raw = this._buf(lv * 2 * this._n), prep = this._buf(lv * 2 * this._n);
+        await this._switchKeyInto(to, from, g, bl, lv, raw);
+        await this._ctx.prepareRelinKeyAsync(raw, prep);
+        raw.free();
+        return this._handle('SwitchKey', { keyId: skTo.keyId, fromKeyId: skFrom.keyId, galoisElement: g, decompBaseLog: bl, decompLevel: lv },
+          { buf: prep, baseLog: bl, level: lv, g });
+      });
+    }
+    /** The Galois keys g_i = n / 2^i + 1 of `steps` trace steps (default log2 n: the full trace) in one buffer */
+    async generateGaloisKeys(sk, steps, options) {
+      this._check();
+      return guard(async () => {
+        const s = this._st(sk, 'SecretKey');
+        const n = this._n, full = Math.log2(n);
+        const st = steps === undefined || steps === null ? full : steps;
+        if (!Number.isInteger(st) || st < 1 || st > full) throw new FHEError('steps must be between 1 and log2(polyDegree)', FHEErrorCode.INVALID_PARAMETERS);
+        const { bl, lv } = this._switchDecomp(options);
+        const per = lv * 2 * n;
+        const raw = this._buf(st * per), prep = this._buf(st * per);
+        for (let i = 0; i < st; i++) await this._switchKeyInto(s, s, n / 2 ** i + 1, bl, lv, raw.view(i * per, per));
+        await this._ctx.prepareRelinKeyAsync(raw, prep);
+        raw.free();
+        return this._handle('GaloisKeys', { keyId: sk.keyId, steps: st, decompBaseLog: bl, decompLevel: lv },
+          { buf: prep, baseLog: bl, level: lv, steps: st });
+      });
+    }
+    async _applyKey(ct, key, g) {
+      const a = this._rlwe(ct), k = this._st(key, 'SwitchKey');
+      if (a.comps !== 2) throw new FHEError('key switching takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+      if (ct.isNtt) throw new FHEError('key switching takes coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+      if (k.g !== g) throw new FHEError(`switch key is for Galois element ${k.g}, not ${g}`, FHEErrorCode.INVALID_PARAMETERS);
+      if (ct.keyId !== key.fromKeyId) throw new FHEError('Switch key does not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      const out = this._buf(2 * this._n);
+      await this._ctx.ctGaloisAsync(k.baseLog, g, k.buf, a.buf, 0, out);
+      return this._ct(out, key.keyId, ct.noiseBudget - 1, 1, { packed: a.packed });
+    }
+    /** The encryption of sigma_g(message), X -> X^g; needs mode 'negacyclic' to decrypt for g != 1 */
+    async applyGalois(ct, g, key) {
+      this._check();
+      return guard(async () => this._applyKey(ct, key, g));
+    }
+    /** The same message under the key's target secret key, without decrypting */
+    async reKey(ct, key) {
+      this._check();
+      return guard(async () => {
+        if (this._st(key, 'SwitchKey').g !== 1) throw new FHEError('reKey needs a switch key with Galois element 1', FHEErrorCode.INVALID_PARAMETERS);
+        return this._applyKey(ct, key, 1);
+      });
+    }
+    /** Every slot of the packed message but `slot` becomes 0: rotate by X^-slot, the
+     *  full trace, rotate back.  Needs the log2(n) keys of generateGaloisKeys(sk)
+     *  and mode 'negacyclic'. */
+    async isolateSlot(ct, slot, keys) {
+      this._check();
+      return guard(async () => {
+        const a = this._rlwe(ct), k = this._st(keys, 'GaloisKeys'), n = this._n;
+        if (this._mode !== 1) throw new FHEError('isolateSlot needs mode negacyclic', FHEErrorCode.INVALID_PARAMETERS);
+        if (a.comps !== 2 || ct.isNtt) throw new FHEError('isolateSlot takes degree-1 coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+        if (!Number.isInteger(slot) || slot < 0 || slot >= n) throw new FHEError('slot index out of range', FHEErrorCode.INVALID_PARAMETERS);
+        if (k.steps !== Math.log2(n)) throw new FHEError('isolateSlot needs the log2(polyDegree) keys of the full trace', FHEErrorCode.INVALID_PARAMETERS);
+        if (ct.keyId !== keys.keyId) throw new FHEError('Galois keys do not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+        // X^-slot = -X^(n - slot): the ring product with a monomial is the exact rotation
+        const rotate = async (src, index, value) => {
+          const mono = new BigUint64Array(2 * n);
+          mono[index] = value;
+          mono[n + index] = value;
+          const rep = this._upload(mono), dst = this._buf(2 * n);
+          await this._ctx.polymulAsync(src, rep, dst);
+          rep.free();
+          return dst;
+        };
+        const x = slot ? await rotate(a.buf, n - slot, this._q - 1n) : a.buf;
+        const y = this._buf(2 * n);
+        await this._ctx.ctTraceAsync(k.baseLog, k.steps, k.buf, x, y);
+        const out = slot ? await rotate(y, slot, 1n) : y;
+        if (slot) { x.free(); y.free(); }
+        return this._ct(out, ct.keyId, ct.noiseBudget - k.steps - 1, 1, { packed: true });
+      });
+    }
+
     // ---- serialisation: binary = header words + the native words, checksum = SHA-256
     _serialize(kind, h, words, meta, opts) {
       const fmt = (opts && opts.format) || 'binary';

@@ -1709,6 +1709,69 @@ static napi_value ctx_lwe_pack(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[7], keep, 4);
 }
 
+/* ---- Galois automorphisms and key switching (fhe_poly_galois_batch,
+ * fhe_ct_galois_batch, fhe_ct_trace_batch) ---- */
+/* polyGalois(a [batch][n], g, out): out = sigma_g(a), X -> X^g for odd g < 2n */
+static int run_poly_galois(job *j) {
+    return fhe_poly_galois_batch(j->c, (uint32_t)j->v[0], j->p[0], j->p[1], j->batch, j->where);
+}
+static napi_value ctx_poly_galois(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 3, &k)) return NULL;
+    uint64_t *a, *o, g;
+    size_t na, no;
+    if (arr_arg(env, &k, 0, &a, &na) || num_arg(env, &k, 1, &g) || arr_arg(env, &k, 2, &o, &no) || na != no ||
+        na == 0 || na % k.n || g >> 32)
+        return bad_args(env, "polyGalois(a [batch*n], g, out [batch*n])"), NULL;
+    job *j = job_new(&k, run_poly_galois, NULL);
+    j->p[0] = a; j->p[1] = o; j->v[0] = g; j->batch = na / k.n;
+    return job_go(env, &k, j, k.argv[2], k.argv, 3);
+}
+/* ctGalois(baseLog, g, swkPrep [level][2][n], ct [batch][2][n], addInput, out [batch][2][n]): the key switch of
+ * sigma_g(ct) (+ ct with addInput) under the prepared switch key */
+static int run_ct_galois(job *j) {
+    return fhe_ct_galois_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], (uint32_t)j->v[2], j->v[1] ? j->p[0] : NULL,
+                               j->p[1], (int)j->v[3], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_galois(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 6, &k)) return NULL;
+    uint64_t bl, g, *key, *ct, add, *o;
+    size_t nk, nc, no;
+    if (num_arg(env, &k, 0, &bl) || num_arg(env, &k, 1, &g) || arr_arg(env, &k, 2, &key, &nk) ||
+        arr_arg(env, &k, 3, &ct, &nc) || num_arg(env, &k, 4, &add) || arr_arg(env, &k, 5, &o, &no) || g >> 32)
+        return bad_args(env, "ctGalois(baseLog, g, swkPrep [level*2n], ct [batch*2n], addInput, out [batch*2n])"), NULL;
+    if (nc == 0 || nc % (2 * k.n) || no != nc || nk % (2 * k.n))
+        return range_err(env, "swkPrep [level][2][n], ct [batch][2][n], out [batch][2][n]");
+    job *j = job_new(&k, run_ct_galois, NULL);
+    j->p[0] = key; j->p[1] = ct; j->p[2] = o;
+    j->v[0] = bl; j->v[1] = nk / (2 * k.n); j->v[2] = g; j->v[3] = add ? 1 : 0; j->batch = nc / (2 * k.n);
+    napi_value keep[3] = {k.argv[2], k.argv[3], k.argv[5]};
+    return job_go(env, &k, j, k.argv[5], keep, 3);
+}
+/* ctTrace(baseLog, steps, keysPrep [steps][level][2][n], ct [batch][2][n], out [batch][2][n]): `steps` steps of the
+ * field trace; key i is the prepared Galois key of g_i = n / 2^i + 1 */
+static int run_ct_trace(job *j) {
+    return fhe_ct_trace_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], (uint32_t)j->v[2], j->v[1] ? j->p[0] : NULL,
+                              j->p[1], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_trace(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 5, &k)) return NULL;
+    uint64_t bl, steps, *key, *ct, *o;
+    size_t nk, nc, no;
+    if (num_arg(env, &k, 0, &bl) || num_arg(env, &k, 1, &steps) || arr_arg(env, &k, 2, &key, &nk) ||
+        arr_arg(env, &k, 3, &ct, &nc) || arr_arg(env, &k, 4, &o, &no) || steps == 0 || steps > 32)
+        return bad_args(env, "ctTrace(baseLog, steps, keysPrep [steps*level*2n], ct [batch*2n], out [batch*2n])"), NULL;
+    if (nc == 0 || nc % (2 * k.n) || no != nc || nk % (steps * 2 * k.n))
+        return range_err(env, "keysPrep [steps][level][2][n], ct [batch][2][n], out [batch][2][n]");
+    job *j = job_new(&k, run_ct_trace, NULL);
+    j->p[0] = key; j->p[1] = ct; j->p[2] = o;
+    j->v[0] = bl; j->v[1] = nk / (steps * 2 * k.n); j->v[2] = steps; j->batch = nc / (2 * k.n);
+    napi_value keep[3] = {k.argv[2], k.argv[3], k.argv[4]};
+    return job_go(env, &k, j, k.argv[4], keep, 3);
+}
+
 /* ---- randomness and key material (fhe_sample_batch, fhe_*_generate) ---- */
 /* sample(kind, seed, stream, noiseStd, out) */
 static int run_sample(job *j) {
@@ -1763,6 +1826,30 @@ static napi_value ctx_ek_gen(napi_env env, napi_callback_info info) {
     j->p[0] = sk; j->p[1] = o; j->v[1] = stream; j->v[2] = bl; j->v[3] = lv; j->d = sd; memcpy(j->v + 6, seed, 32);
     napi_value keep[2] = {k.argv[0], k.argv[6]};
     return job_go(env, &k, j, k.argv[6], keep, 2);
+}
+/* switchKeyGenerate(skTo [n], skFrom [n], g, baseLog, level, seed, stream, noiseStd, out [level][2][n]): the key
+ * that switches sigma_g(ct) from sigma_g(skFrom) to skTo (fhe_switch_key_generate) */
+static int run_swk_gen(job *j) {
+    return fhe_switch_key_generate(j->c, j->p[0], j->p[1], (uint32_t)j->v[4], (uint32_t)j->v[2], (uint32_t)j->v[3],
+                                   j->v + 6, j->v[1], j->d, j->p[2], j->where);
+}
+static napi_value ctx_swk_gen(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 9, &k)) return NULL;
+    uint64_t seed[4], stream, g, bl, lv, *st, *sf, *o;
+    size_t nt, nf, no;
+    double sd;
+    if (arr_arg(env, &k, 0, &st, &nt) || arr_arg(env, &k, 1, &sf, &nf) || num_arg(env, &k, 2, &g) ||
+        num_arg(env, &k, 3, &bl) || num_arg(env, &k, 4, &lv) || seed_arg(env, &k, 5, seed) ||
+        num_arg(env, &k, 6, &stream) || dbl_arg(env, &k, 7, &sd) || arr_arg(env, &k, 8, &o, &no) || nt != k.n ||
+        nf != k.n || no != lv * 2 * k.n || g >> 32)
+        return bad_args(env, "switchKeyGenerate(skTo [n], skFrom [n], g, baseLog, level, seed, stream, noiseStd, "
+                             "out [level][2][n])"), NULL;
+    job *j = job_new(&k, run_swk_gen, NULL);
+    j->p[0] = st; j->p[1] = sf; j->p[2] = o;
+    j->v[1] = stream; j->v[2] = bl; j->v[3] = lv; j->v[4] = g; j->d = sd; memcpy(j->v + 6, seed, 32);
+    napi_value keep[3] = {k.argv[0], k.argv[1], k.argv[8]};
+    return job_go(env, &k, j, k.argv[8], keep, 3);
 }
 /* ggswEncrypt(values: BigInt64Array [count], sk [n], k, baseLog, level, seed, stream, noiseStd,
  * out [count][(k+1)L][k+1][n]) */
@@ -1980,6 +2067,10 @@ static napi_value init(napi_env env, napi_value exports) {
         M("lweSum", ctx_lwe_sum),
         M("lwePack", ctx_lwe_pack),
         M("packKeyGenerate", ctx_pack_key_gen),
+        M("polyGalois", ctx_poly_galois),
+        M("ctGalois", ctx_ct_galois),
+        M("ctTrace", ctx_ct_trace),
+        M("switchKeyGenerate", ctx_swk_gen),
         M("sample", ctx_sample),
         M("publicKeyGenerate", ctx_pk_gen),
         M("evalKeyGenerate", ctx_ek_gen),
