@@ -310,6 +310,83 @@ int fhe_ct_square_relin_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, c
                               const uint64_t *ref, size_t ref_count, const uint64_t *rlk_ntt,
                               uint64_t *out, size_t batch, int where);
 
+/* ---- scale-invariant BFV multiplication ----------------------------------
+ * fhe_ct_multiply_batch, fhe_ct_dot_batch and fhe_ct_square_batch are the
+ * reference's multiply: the tensor product mod q, whose result carries
+ * Delta^2 m.  The calls below are the BFV product round(t/q (ct1 (x) ct2))
+ * taken over the integers, whose result carries Delta m and decrypts with
+ * real keys and real noise.  They are new entry points; the words of the
+ * calls above are unchanged.
+ *
+ * Definition (exact integers).  q is the context modulus (odd), t the
+ * plaintext modulus (0 selects 4), 2 <= t < q.
+ *   lift(x), any u64 x: r = x mod q; r when r <= (q-1)/2, else r - q.
+ *   For a = (a0, a1), b = (b0, b1) and (*) the negacyclic product in
+ *   Z[X]/(X^n + 1) over the integers:
+ *     X0 = lift(a0) (*) lift(b0)
+ *     X1 = lift(a0) (*) lift(b1) + lift(a1) (*) lift(b0)
+ *     X2 = lift(a1) (*) lift(b1)
+ *   rnd(Y) = the integer nearest to Y / q (no ties: q is odd).
+ *   out word = rnd(t X) mod q, canonical in [0, q).
+ * fhe_ct_dot_scaled_batch rescales ONCE, after summing: out[g] = rnd(t sum_i
+ * X_i) mod q.  Rounding is not linear, so this is NOT word-identical to a sum
+ * of fhe_ct_multiply_scaled_batch results: it carries one rounding error
+ * instead of `count` (the same kind of difference as the lazy relinearisation
+ * of fhe_ct_dot_batch).  fhe_ct_square_scaled_batch is the multiply of d = ct
+ * - ref (fhe_poly_sub_batch) with itself, word for word.
+ *
+ * Opening.  The phase of the result is c0 - c1 s + c2 s^2, the sign that
+ * fhe_relinearize_batch implements.  The reference's degree-2 decrypt
+ * SUBTRACTS c2 s^2, so fhe_decrypt_batch(components = 3) is not the way to
+ * open these: relinearise first (fhe_relinearize_batch, unchanged) and
+ * decrypt the degree-1 result.
+ *
+ * Contexts.  FHE_MODE_NEGACYCLIC only (a compat context fails at creation
+ * with FHE_ERR_UNSUPPORTED: the rescale has a meaning only under the true ring
+ * product), coefficient form only, single-device contexts only
+ * (FHE_ERR_UNSUPPORTED for a multi-device one).  Every n and odd q the
+ * negacyclic context takes.  The scale context BORROWS ctx, follows ctx's
+ * stream at every call, and must be destroyed before ctx.
+ *
+ * Method.  The tensor runs in three channels with the existing kernels: mod q
+ * on ctx, and mod two auxiliary NTT primes (fhe_scale_info.aux; fixed library
+ * constants below 2^62, = 1 mod 2^17, different from q) on two auxiliary
+ * contexts, fed by fhe_poly_center_lift_batch's kernel.  Reduction Z -> Z_p
+ * commutes with (*), so each channel is exact, and fhe_poly_scale_round_batch's
+ * kernel recovers rnd(t X) from the three residues as long as
+ * t count n q < aux[0] aux[1] (about 2^122).  max_count is the largest such
+ * count; a larger count answers FHE_ERR_UNSUPPORTED and the message names it;
+ * a (q, t, n) with max_count 0 fails at creation.  When t count n q < aux[0]
+ * the first auxiliary prime alone determines the result and only its channel
+ * runs (decided per call; the words are the same by definition).  Batches run in chunks of
+ * pairs with stream-ordered temporaries of at most 1 GiB; FHE_SCALE_CHUNK=
+ * <pairs> forces the chunk (read per call).  FHE_HOST stages chunk by chunk.
+ *
+ * FHE_ERR_INVALID_ARG: a null pointer; batch, count, groups or npoly 0; a bad
+ * ref_count (as fhe_ct_square_batch); an output overlapping an input; t < 2 or
+ * t >= q; device buffers not 16-byte aligned.  The null and zero-count checks
+ * come before the context is looked at. */
+typedef struct fhe_scale_ctx fhe_scale_ctx;
+typedef struct { uint64_t q, t, aux[2]; uint32_t n, naux; uint64_t max_count; } fhe_scale_info;
+int fhe_scale_ctx_create(fhe_ctx *ctx, uint64_t t, fhe_scale_ctx **out);
+void fhe_scale_ctx_destroy(fhe_scale_ctx *sc);
+int fhe_scale_ctx_get_info(const fhe_scale_ctx *sc, fhe_scale_info *info);
+/* the two kernels, callable on their own.  in [npoly][n], any u64 words ->
+ * out_p1, out_p2 [npoly][n] = lift(in) mod aux[0], mod aux[1], canonical */
+int fhe_poly_center_lift_batch(fhe_scale_ctx *sc, const uint64_t *in, uint64_t *out_p1, uint64_t *out_p2, size_t npoly, int where);
+/* the lift of ct - ref (mod_sub, then lift): ct [batch][2][n], ref / ref_count as fhe_ct_square_batch */
+int fhe_ct_center_lift_batch(fhe_scale_ctx *sc, const uint64_t *ct, const uint64_t *ref, size_t ref_count, uint64_t *out_p1, uint64_t *out_p2, size_t batch, int where);
+/* xq, xp1, xp2 [npoly][n]: X mod q, mod aux[0], mod aux[1] (any u64 words,
+ * read mod their modulus) -> out [npoly][n] = rnd(t X) mod q for the X with
+ * |rnd(t X)| < aux[0] aux[1] / 2 */
+int fhe_poly_scale_round_batch(fhe_scale_ctx *sc, const uint64_t *xq, const uint64_t *xp1, const uint64_t *xp2, uint64_t *out, size_t npoly, int where);
+/* ct1, ct2 [batch][2][n] -> out [batch][3][n] */
+int fhe_ct_multiply_scaled_batch(fhe_scale_ctx *sc, const uint64_t *ct1, const uint64_t *ct2, uint64_t *out, size_t batch, int where);
+/* a, b [groups][count][2][n] -> out [groups][3][n], one rescale per group */
+int fhe_ct_dot_scaled_batch(fhe_scale_ctx *sc, const uint64_t *a, const uint64_t *b, size_t count, size_t groups, uint64_t *out, int where);
+/* square(ct - ref), ref / ref_count as fhe_ct_square_batch */
+int fhe_ct_square_scaled_batch(fhe_scale_ctx *sc, const uint64_t *ct, const uint64_t *ref, size_t ref_count, uint64_t *out, size_t batch, int where);
+
 /* ---- ciphertext tally (encryption.cpp:1061-1067, 1153-1168, 1327-1460) ---
  * EncryptionEngine::batch_add / batch_add_tree / tally_votes /
  * tally_multi_candidate: the sum of `count` ciphertexts of `polys` (1..3)

@@ -336,4 +336,24 @@ hipError_t launch_lwe_pack(const ModConsts &m, uint32_t base_log, uint32_t level
 hipError_t launch_decompose(const ModConsts &m, const uint64_t *poly, uint64_t *out, uint32_t n, size_t npoly,
                             uint32_t base_log, uint32_t level, hipStream_t s);
 
+// Scale-invariant BFV product (bfv_scale.hip).  Constants per (q, t) and the
+// two auxiliary primes p[0], p[1] (odd, below 2^62); "R" is 2^64 and every
+// *_q / *_p product constant is in Montgomery form for wmont.
+struct ScaleConsts {
+    uint64_t q, half_q, mu_q, qinv_q;  // (q - 1) / 2, floor(2^64 / q), -q^-1 mod 2^64
+    uint64_t t_q, p1_q, pp_q;          // t R mod q, p1 R mod q, p1 p2 mod q (plain)
+    uint64_t p[2], mu_p[2], qinv_p[2]; // p_j, floor(2^64 / p_j), -p_j^-1 mod 2^64
+    uint64_t t_p[2], qi_p[2];          // t R mod p_j, q^-1 R mod p_j
+    uint64_t p1inv_p2;                 // p1^-1 R mod p2
+    uint64_t half_hi, half_lo;         // (p1 p2 - 1) / 2
+};
+// lift((in - ref) mod q) mod p1 / p2 over `words` words (even; 16-byte aligned
+// buffers): ref nullable; word w belongs to ciphertext w / ct_words, whose
+// reference starts at ref + (w / ct_words) ref_stride (0 shares one).
+hipError_t launch_center_lift(const ScaleConsts &k, const uint64_t *in, const uint64_t *ref, size_t ref_stride,
+                              size_t ct_words, uint64_t *out1, uint64_t *out2, size_t words, hipStream_t s);
+// out = round(t X / q) mod q from X mod q, X mod p1, X mod p2; out may be xq.
+hipError_t launch_scale_round(const ScaleConsts &k, const uint64_t *xq, const uint64_t *x1, const uint64_t *x2,
+                              uint64_t *out, size_t words, hipStream_t s);
+
 }  // namespace FHE_NS

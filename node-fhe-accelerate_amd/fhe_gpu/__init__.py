@@ -85,6 +85,13 @@ class CtxInfo(C.Structure):
     ]
 
 
+class ScaleInfo(C.Structure):
+    _fields_ = [
+        ("q", C.c_uint64), ("t", C.c_uint64), ("aux", C.c_uint64 * 2), ("n", C.c_uint32), ("naux", C.c_uint32),
+        ("max_count", C.c_uint64),
+    ]
+
+
 u64p = C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
@@ -148,6 +155,15 @@ SIGNATURES = [
     ("fhe_ct_square_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]),
     ("fhe_ct_square_relin_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_scale_ctx_create", C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
+    ("fhe_scale_ctx_destroy", None, [vp]),
+    ("fhe_scale_ctx_get_info", C.c_int, [vp, C.POINTER(ScaleInfo)]),
+    ("fhe_poly_center_lift_batch", C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_center_lift_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_poly_scale_round_batch", C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_multiply_scaled_batch", C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_dot_scaled_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int]),
+    ("fhe_ct_square_scaled_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int]),
     ("fhe_glwe_rotate_batch", C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_cmux_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_blind_rotate_batch", C.c_int,
@@ -1199,6 +1215,131 @@ class DecryptionResult:
                       self.success.reshape(-1)]
 
 
+class ScaledMultiplier:
+    """The scale-invariant BFV product round(t/q (ct1 (x) ct2)) over the
+    integers (fhe_scale_ctx): the result carries Delta m, not the Delta^2 m
+    of EncryptionEngine.multiply, and decrypts with real keys after
+    relinearisation.  Negacyclic single-device rings only.  Owns the scale
+    context (two auxiliary NTT contexts on the ring's device); it borrows
+    ``ring`` and keeps it alive."""
+
+    def __init__(self, ring: "PolynomialRing", t: int = 0):
+        self._h = None
+        h = C.c_void_p()
+        _check(lib().fhe_scale_ctx_create(ring._h, int(t), C.byref(h)))
+        self._h = h
+        self.ring = ring
+        info = ScaleInfo()
+        _check(lib().fhe_scale_ctx_get_info(h, C.byref(info)))
+        self.t, self.aux, self.max_count = int(info.t), (int(info.aux[0]), int(info.aux[1])), int(info.max_count)
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib is not None:
+            _lib.fhe_scale_ctx_destroy(h)
+        self._h = None
+
+    __del__ = close
+
+    def _run(self, fn, ins, outs, args_of):
+        bi = [None if x is None else _Buf(x) for x in ins]
+        bo = [_Buf(x, True) for x in outs]
+        w = _where(*bi, *bo)
+        self.ring._bind_stream(w)
+        _check(fn(*args_of([b.ptr if b is not None else None for b in bi], [b.ptr for b in bo], w)))
+
+    def center_lift(self, polys, ref=None):
+        """lift(x) mod aux[0], mod aux[1] of rows [..., n] (any u64 words);
+        with ref, rows [..., 2, n] of ciphertexts and the lift of ct - ref
+        (ref one ciphertext [2, n] for all, or one per ciphertext)."""
+        r = self.ring
+        polys = _as_u64(polys)
+        o1, o2 = _like(polys), _like(polys)
+        if ref is None:
+            nb = r._batch(polys)
+            self._run(lib().fhe_poly_center_lift_batch, [polys], [o1, o2],
+                      lambda i, o, w: (self._h, i[0], o[0], o[1], nb, w))
+        else:
+            nb = _lead(polys, (2, r.degree))
+            ref = _as_u64(ref)
+            cnt = 1 if tuple(ref.shape) == (2, r.degree) else _lead(ref, (2, r.degree))
+            self._run(lib().fhe_ct_center_lift_batch, [polys, ref], [o1, o2],
+                      lambda i, o, w: (self._h, i[0], i[1], cnt, o[0], o[1], nb, w))
+        return o1, o2
+
+    def scale_round(self, xq, xp1, xp2, out=None):
+        """round(t X / q) mod q from X mod q, mod aux[0], mod aux[1], rows [..., n]."""
+        xq, xp1, xp2 = _as_u64(xq), _as_u64(xp1), _as_u64(xp2)
+        nb = self.ring._batch(xq)
+        if tuple(xp1.shape) != tuple(xq.shape) or tuple(xp2.shape) != tuple(xq.shape):
+            raise FHEError(-9, "operand shapes differ")
+        out = _like(xq) if out is None else out
+        self._run(lib().fhe_poly_scale_round_batch, [xq, xp1, xp2], [out],
+                  lambda i, o, w: (self._h, i[0], i[1], i[2], o[0], nb, w))
+        return out
+
+    def multiply(self, ct1, ct2, out=None):
+        """[..., 2, n] x [..., 2, n] -> [..., 3, n]; phase c0 - c1 s + c2 s^2."""
+        r = self.ring
+        ct1, ct2 = _as_u64(ct1), _as_u64(ct2)
+        nb = _lead(ct1, (2, r.degree))
+        if tuple(ct2.shape) != tuple(ct1.shape):
+            raise FHEError(-9, "ciphertext shapes differ")
+        if out is None:
+            out = _empty(ct1, tuple(ct1.shape[:-2]) + (3, r.degree))
+        self._run(lib().fhe_ct_multiply_scaled_batch, [ct1, ct2], [out],
+                  lambda i, o, w: (self._h, i[0], i[1], o[0], nb, w))
+        return out
+
+    def dot(self, cts1, cts2, out=None, grouped=None):
+        """sum_i cts1[i] (x) cts2[i] with ONE rescale after the sum: [count, 2,
+        n] -> [3, n], or [groups, count, 2, n] -> [groups, 3, n].  Not the
+        words of a sum of multiply() results (rounding is not linear): one
+        rounding error instead of count."""
+        r = self.ring
+        cts1, cts2 = _as_u64(cts1), _as_u64(cts2)
+        shape = tuple(cts1.shape)
+        grouped = len(shape) == 4 if grouped is None else bool(grouped)
+        lead = 2 if grouped else 1
+        if len(shape) != lead + 2 or shape[lead:] != (2, r.degree):
+            raise FHEError(-9, "ciphertexts must be [count, 2, n] or [groups, count, 2, n]")
+        if tuple(cts2.shape) != shape:
+            raise FHEError(-9, "ciphertext shapes differ")
+        groups, count = (shape[0], shape[1]) if grouped else (1, shape[0])
+        oshape = ((groups,) if grouped else ()) + (3, r.degree)
+        if out is None:
+            out = _empty(cts1, oshape)
+        elif tuple(out.shape) != oshape:
+            raise FHEError(-9, f"out must have shape {list(oshape)}")
+        self._run(lib().fhe_ct_dot_scaled_batch, [cts1, cts2], [out],
+                  lambda i, o, w: (self._h, i[0], i[1], count, groups, o[0], w))
+        return out
+
+    def squared_difference(self, cts, expected, out=None):
+        """square(cts - expected): expected None, one ciphertext [2, n] for
+        all, or one per ciphertext.  The words of multiply(d, d), d = cts - expected."""
+        r = self.ring
+        cts = _as_u64(cts)
+        nb = _lead(cts, (2, r.degree))
+        cnt = 0
+        if expected is not None:
+            expected = _as_u64(expected)
+            if tuple(expected.shape) == (2, r.degree):
+                cnt = 1
+            elif tuple(expected.shape) != tuple(cts.shape):
+                raise FHEError(-9, "ciphertext shapes differ")
+            else:
+                cnt = nb
+        if out is None:
+            out = _empty(cts, tuple(cts.shape[:-2]) + (3, r.degree))
+        self._run(lib().fhe_ct_square_scaled_batch, [cts, expected], [out],
+                  lambda i, o, w: (self._h, i[0], i[1], cnt, o[0], nb, w))
+        return out
+
+    def square(self, ct, out=None):
+        return self.squared_difference(ct, None, out)
+
+
 class EncryptionEngine:
     """Ciphertext arithmetic of EncryptionEngine (encryption.cpp:594-980) over
     batches of ciphertexts [..., 2, n] (c0, c1) / [..., 3, n] (degree 2), and
@@ -1731,6 +1872,48 @@ class EncryptionEngine:
     def square_relin(self, ct, ek: EvaluationKey, out=None):
         """square_relin (:1037-1055)."""
         return self.compute_anomaly_score(ct, None, ek, out)
+
+    # -- scale-invariant products (ScaledMultiplier with this engine's t): results carry Delta m and
+    # decrypt with real keys after relinearize(); negacyclic rings only
+    @property
+    def scaled(self) -> "ScaledMultiplier":
+        if getattr(self, "_scaled", None) is None:
+            self._scaled = ScaledMultiplier(self.ring, self.t)
+        return self._scaled
+
+    def multiply_scaled(self, ct1, ct2, out=None):
+        """round(t/q (ct1 (x) ct2)) -> [..., 3, n] (ScaledMultiplier.multiply)."""
+        return self.scaled.multiply(ct1, ct2, out)
+
+    def dot_scaled(self, cts1, cts2, out=None, grouped=None):
+        """Inner product with one rescale after the sum (ScaledMultiplier.dot)."""
+        return self.scaled.dot(cts1, cts2, out, grouped)
+
+    def square_scaled(self, ct, out=None):
+        return self.scaled.squared_difference(ct, None, out)
+
+    def squared_difference_scaled(self, cts, expected, out=None):
+        return self.scaled.squared_difference(cts, expected, out)
+
+    def multiply_relin_scaled(self, ct1, ct2, ek: EvaluationKey, out=None):
+        """relinearize(multiply_scaled(ct1, ct2)) -> [..., 2, n]."""
+        return self.relinearize(self.multiply_scaled(ct1, ct2), ek, out)
+
+    def tally_weighted_votes_scaled(self, ballots, weights, ek: EvaluationKey, out=None):
+        """sum_i ballots[i] * weights[i] under encrypted weights as a degree-1
+        ciphertext [2, n] that decrypts with real keys: dot_scaled, then one
+        relinearisation."""
+        if len(ballots) != len(weights):
+            raise FHEError(-9, "Ballots and weights must have the same size")
+        if len(ballots) == 0:
+            raise FHEError(-9, "Cannot tally empty ballot list")
+        stack = lambda x: (torch.stack(list(x)) if all(_is_tensor(c) for c in x)
+                           else np.stack([np.asarray(c, dtype=np.uint64) for c in x]))
+        if isinstance(ballots, (list, tuple)):
+            ballots = stack(ballots)
+        if isinstance(weights, (list, tuple)):
+            weights = stack(weights)
+        return self.relinearize(self.dot_scaled(ballots, weights, grouped=False), ek, out)
 
     def pack_lwe(self, lwe_a, lwe_b, slots, pack_key: "PackKey", out=None, accumulate: bool = False):
         """The packing key switch (fhe_lwe_pack_batch): LWE ciphertexts

@@ -251,6 +251,8 @@ export interface FHETallyEngine extends FHEEngine {
  * noise, not the same words (the digit decomposition is not linear). */
 export interface TallyWeightedOptions {
   relinearize?: 'each' | 'once';
+  /** dotProductScaled and one relinearisation (FHEScaledEngine): opens to sum w_i b_i with real keys */
+  scaled?: boolean;
 }
 
 /** Ciphertext inner product: sum_i multiply(cts1[i], cts2[i]) as one degree-2
@@ -365,6 +367,20 @@ export interface FHEGaloisEngine extends FHEPackEngine {
   isolateSlot(ct: Ciphertext, slot: number, keys: GaloisKeys): Promise<Ciphertext>;
 }
 
+/** Scale-invariant BFV products (fhe_ct_multiply_scaled_batch, fhe_ct_dot_scaled_batch,
+ * fhe_ct_square_scaled_batch): round(t/q (ct1 (x) ct2)) over the integers.  The degree-2 result
+ * carries Delta m (multiply()'s carries Delta^2 m) and opens with real keys after relinearize();
+ * its phase is c0 - c1 s + c2 s^2, so decrypt() of the degree-2 result itself does not open it.
+ * dotProductScaled rescales once after the sum: not the words of a sum of multiplyScaled().
+ * Mode 'negacyclic', coefficient form, single device. */
+export interface FHEScaledEngine extends FHEGaloisEngine {
+  multiplyScaled(ct1: Ciphertext, ct2: Ciphertext): Promise<Ciphertext>;
+  dotProductScaled(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  squareScaled(ct: Ciphertext): Promise<Ciphertext>;
+  tallyWeightedVotes(ballots: Ciphertext[], weights: Ciphertext[], ek: EvaluationKey,
+    progress?: ProgressCallback, options?: TallyWeightedOptions): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -443,6 +459,9 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   applyGalois(ct: Ciphertext, g: number, key: SwitchKey): Promise<Ciphertext>;
   reKey(ct: Ciphertext, key: SwitchKey): Promise<Ciphertext>;
   isolateSlot(ct: Ciphertext, slot: number, keys: GaloisKeys): Promise<Ciphertext>;
+  multiplyScaled(ct1: Ciphertext, ct2: Ciphertext): Promise<Ciphertext>;
+  dotProductScaled(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
+  squareScaled(ct: Ciphertext): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension); part names another
    * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
   deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
@@ -586,6 +605,16 @@ export declare class NttContext {
    * g_i = n / 2^i + 1 (fhe_ct_trace_batch). */
   ctTrace(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Words;
   ctTraceAsync(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Promise<Words>;
+  /** Scale-invariant products round(t/q (ct1 (x) ct2)) (t: plaintext modulus, 0 selects 4); the
+   * context keeps one scale context per t.  ct [batch][2][n] -> out [batch][3][n] */
+  ctMultiplyScaled(t: bigint | number, ct1: Words, ct2: Words, out: Words): Words;
+  ctMultiplyScaledAsync(t: bigint | number, ct1: Words, ct2: Words, out: Words): Promise<Words>;
+  /** a, b [groups][count][2][n] -> out [groups][3][n], one rescale per group */
+  ctDotScaled(t: bigint | number, a: Words, b: Words, count: number, out: Words): Words;
+  ctDotScaledAsync(t: bigint | number, a: Words, b: Words, count: number, out: Words): Promise<Words>;
+  /** square(ct - ref), ref as ctSquare */
+  ctSquareScaled(t: bigint | number, ct: Words, ref: Words | null, out: Words): Words;
+  ctSquareScaledAsync(t: bigint | number, ct: Words, ref: Words | null, out: Words): Promise<Words>;
   relinearize(ct3: Words, rlk: Words, baseLog: number, out: Words): Words;
   externalProduct(glwe: Words, ggsw: Words, baseLog: number, level: number, out: Words): Words;
   blindRotate(acc: Words, lweA: Words, lweB: Words, bsk: Words, baseLog: number, level: number): Words;

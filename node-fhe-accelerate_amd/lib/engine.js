@@ -755,6 +755,14 @@ function makeEngineClass(native) {
       const start = Date.now(), total = ballots.length;
       const report = (current, of) => progress({ stage: 'tally_weighted_votes', current, total: of,
         elapsedMs: Date.now() - start, progressPercent: (current / of) * 100 });
+      if (options && options.scaled) {
+        // the scale-invariant inner product (one rescale by t/q after the sum),
+        // then one relinearisation: opens to sum w_i b_i with real keys
+        const r = await this.relinearize(await this.dotProductScaled(ballots, weights), ek);
+        for (let i = 0; progress && i < total; i++) if ((i + 1) % 100 === 0) report(i + 1, total * 2);
+        for (let i = 1; progress && i < total; i++) report(total + i, total + total - 1);
+        return r;
+      }
       if (mode === 'once') {
         // lazy relinearisation: the fused degree-2 sum, then one key switch.
         // Same plaintext, less noise; not the words of the per-ballot fold
@@ -813,6 +821,70 @@ function makeEngineClass(native) {
       });
       for (let i = 1; progress && i <= total; i++) {
         progress({ stage: 'dot_product', current: i, total, elapsedMs: Date.now() - start, progressPercent: (i / total) * 100 });
+      }
+      return r;
+    }
+    // ---- scale-invariant BFV products (fhe_ct_multiply_scaled_batch,
+    // fhe_ct_dot_scaled_batch, fhe_ct_square_scaled_batch): round(t/q (ct1 (x)
+    // ct2)) over the integers.  The result carries Delta m (multiply()'s
+    // carries Delta^2 m) and opens with real keys after relinearize(); its
+    // phase is c0 - c1 s + c2 s^2, so decrypt() of the degree-2 result is not
+    // the way to open it.  Mode 'negacyclic', coefficient form, one device.
+    _scaledPair(ct1, ct2) {
+      const a = this._rlwe(ct1), b = this._rlwe(ct2);
+      this._sameKey(ct1, ct2, 'multiply');
+      if (a.comps !== 2 || b.comps !== 2) throw new FHEError('multiply takes degree-1 ciphertexts (relinearize first)', FHEErrorCode.INVALID_PARAMETERS);
+      if (ct1.isNtt || ct2.isNtt) throw new FHEError('scaled products take coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+      return [a, b];
+    }
+    async multiplyScaled(ct1, ct2) {
+      this._check();
+      return guard(async () => {
+        const [a, b] = this._scaledPair(ct1, ct2);
+        const out = this._buf(3 * this._n);
+        await this._ctx.ctMultiplyScaledAsync(this._t, a.buf, b.buf, out);
+        const red = Math.log2(this._n) + 5;
+        return this._ct(out, ct1.keyId, Math.min(ct1.noiseBudget, ct2.noiseBudget) - red, 2, { packed: a.packed || b.packed });
+      });
+    }
+    async squareScaled(ct) {
+      this._check();
+      return guard(async () => {
+        const [a] = this._scaledPair(ct, ct);
+        const out = this._buf(3 * this._n);
+        await this._ctx.ctSquareScaledAsync(this._t, a.buf, null, out);
+        return this._ct(out, ct.keyId, ct.noiseBudget - (Math.log2(this._n) + 5), 2, { packed: a.packed });
+      });
+    }
+    /** sum_i cts1[i] (x) cts2[i] with ONE rescale after the sum: one rounding
+     *  error instead of count, so not the words of a sum of multiplyScaled() */
+    async dotProductScaled(cts1, cts2, progress) {
+      this._check();
+      if (!Array.isArray(cts1) || !Array.isArray(cts2) || cts1.length !== cts2.length) {
+        throw new FHEError('Ballots and weights must have the same size', FHEErrorCode.INVALID_PARAMETERS);
+      }
+      if (cts1.length === 0) throw new FHEError('Cannot tally empty ballot list', FHEErrorCode.INVALID_PARAMETERS);
+      const start = Date.now(), total = cts1.length, w = 2 * this._n;
+      const r = await guard(async () => {
+        const A = this._buf(total * w), B = this._buf(total * w);
+        let budget = Infinity, packed = false;
+        for (let i = 0; i < total; i++) {
+          const [a, b] = this._scaledPair(cts1[i], cts2[i]);
+          if (i > 0) this._sameKey(cts1[0], cts1[i], 'add');
+          A.copyFrom(a.buf, i * w);
+          B.copyFrom(b.buf, i * w);
+          packed = packed || a.packed || b.packed;
+          budget = Math.min(budget, cts1[i].noiseBudget, cts2[i].noiseBudget);
+        }
+        const out = this._buf(3 * this._n);
+        await this._ctx.ctDotScaledAsync(this._t, A, B, total, out);
+        A.free();
+        B.free();
+        const red = Math.log2(this._n) + 5 + Math.ceil(Math.log2(total));
+        return this._ct(out, cts1[0].keyId, budget - red, 2, { packed });
+      });
+      for (let i = 1; progress && i <= total; i++) {
+        progress({ stage: 'dot_product_scaled', current: i, total, elapsedMs: Date.now() - start, progressPercent: (i / total) * 100 });
       }
       return r;
     }

@@ -296,13 +296,19 @@ static napi_value ma_get_modulus(napi_env env, napi_callback_info info) {
  * it (refcounted on the JS thread, where all finalizers run); `mu`
  * serialises the jobs of one context (each job's launches and its final
  * stream synchronisation form one unit). */
+#define MAXSCALE 4
 typedef struct {
     fhe_ctx *c;
     int refs;
     pthread_mutex_t mu;
+    /* scale contexts of the scaled products, one per plaintext modulus, made on first use under mu */
+    fhe_scale_ctx *sc[MAXSCALE];
+    uint64_t sc_t[MAXSCALE];
+    int nsc;
 } nctx;
 static void nctx_release(nctx *k) {
     if (--k->refs == 0) {
+        for (int i = 0; i < k->nsc; ++i) fhe_scale_ctx_destroy(k->sc[i]); /* they borrow k->c */
         fhe_ctx_destroy(k->c);
         pthread_mutex_destroy(&k->mu);
         free(k);
@@ -1270,6 +1276,94 @@ static napi_value ctx_ct_square(napi_env env, napi_callback_info info) {
     napi_value keep[3] = {k.argv[0], k.argv[2], k.argv[1]};  /* a null ref is not kept */
     return job_go(env, &k, j, k.argv[2], keep, r ? 3 : 2);
 }
+/* ---- scale-invariant products (fhe_ct_multiply_scaled_batch, fhe_ct_dot_scaled_batch,
+ * fhe_ct_square_scaled_batch): round(t/q (ct1 (x) ct2)), results that carry Delta m.  The scale context
+ * of plaintext modulus t (0: 4) is made on first use and kept with the context; the oldest of
+ * MAXSCALE goes when one more modulus is asked for.  Called under the context lock. */
+static int scale_of(job *j, uint64_t t, fhe_scale_ctx **out) {
+    nctx *k = j->k;
+    if (t == 0) t = 4;
+    for (int i = 0; i < k->nsc; ++i)
+        if (k->sc_t[i] == t) return *out = k->sc[i], 0;
+    fhe_scale_ctx *sc = NULL;
+    int rc = fhe_scale_ctx_create(k->c, t, &sc);
+    if (rc) return rc;
+    if (k->nsc == MAXSCALE) {
+        rc = fhe_ctx_synchronize(k->c);
+        fhe_scale_ctx_destroy(k->sc[0]);
+        memmove(k->sc, k->sc + 1, (MAXSCALE - 1) * sizeof k->sc[0]);
+        memmove(k->sc_t, k->sc_t + 1, (MAXSCALE - 1) * sizeof k->sc_t[0]);
+        k->nsc--;
+    }
+    k->sc[k->nsc] = sc;
+    k->sc_t[k->nsc++] = t;
+    *out = sc;
+    return rc;
+}
+/* ctMultiplyScaled(t, ct1, ct2, out): ct [batch][2][n] -> out [batch][3][n] */
+static int run_ct_mul_scaled(job *j) {
+    fhe_scale_ctx *sc;
+    int rc = scale_of(j, j->v[0], &sc);
+    return rc ? rc : fhe_ct_multiply_scaled_batch(sc, j->p[0], j->p[1], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_mul_scaled(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    uint64_t t, *x, *y, *o;
+    size_t nx, ny, no;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &x, &nx) || arr_arg(env, &k, 2, &y, &ny) || arr_arg(env, &k, 3, &o, &no))
+        return bad_args(env, "ctMultiplyScaled(t, ct1, ct2, out)"), NULL;
+    const size_t per = 2 * k.n;
+    if (nx == 0 || nx % per || ny != nx || no != nx / 2 * 3) return range_err(env, "ciphertexts must be [batch][2][n], out [batch][3][n]");
+    job *j = job_new(&k, run_ct_mul_scaled, NULL);
+    j->p[0] = x; j->p[1] = y; j->p[2] = o; j->v[0] = t; j->batch = nx / per;
+    return job_go(env, &k, j, k.argv[3], k.argv + 1, 3);
+}
+/* ctDotScaled(t, a, b, count, out): a, b [groups][count][2][n] -> out [groups][3][n], one rescale per group */
+static int run_ct_dot_scaled(job *j) {
+    fhe_scale_ctx *sc;
+    int rc = scale_of(j, j->v[0], &sc);
+    return rc ? rc : fhe_ct_dot_scaled_batch(sc, j->p[0], j->p[1], (size_t)j->v[1], j->batch, j->p[2], j->where);
+}
+static napi_value ctx_ct_dot_scaled(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 5, &k)) return NULL;
+    uint64_t t, *x, *y, *o, count;
+    size_t nx, ny, no;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &x, &nx) || arr_arg(env, &k, 2, &y, &ny) || num_arg(env, &k, 3, &count) ||
+        arr_arg(env, &k, 4, &o, &no))
+        return bad_args(env, "ctDotScaled(t, a, b, count, out)"), NULL;
+    const size_t per = 2 * k.n;
+    if (count == 0 || nx == 0 || nx % (per * count) || ny != nx || no != nx / (per * count) * 3 * k.n)
+        return range_err(env, "a, b must be [groups][count][2][n], out [groups][3][n]");
+    job *j = job_new(&k, run_ct_dot_scaled, NULL);
+    j->p[0] = x; j->p[1] = y; j->p[2] = o; j->v[0] = t; j->v[1] = count; j->batch = nx / (per * count);
+    napi_value keep[3] = {k.argv[1], k.argv[2], k.argv[4]};
+    return job_go(env, &k, j, k.argv[4], keep, 3);
+}
+/* ctSquareScaled(t, ct, ref | null, out): square(ct - ref), ref as ctSquare */
+static int run_ct_square_scaled(job *j) {
+    fhe_scale_ctx *sc;
+    int rc = scale_of(j, j->v[0], &sc);
+    return rc ? rc : fhe_ct_square_scaled_batch(sc, j->p[0], j->p[1], (size_t)j->v[1], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_square_scaled(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    uint64_t t, *x, *r = NULL, *o;
+    size_t nx, nr = 0, no;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &x, &nx) || (!undef_arg(env, &k, 2) && arr_arg(env, &k, 2, &r, &nr)) ||
+        arr_arg(env, &k, 3, &o, &no))
+        return bad_args(env, "ctSquareScaled(t, ct, ref | null, out)"), NULL;
+    const size_t per = 2 * k.n;
+    if (nx == 0 || nx % per || no != nx / 2 * 3) return range_err(env, "ciphertexts must be [batch][2][n], out [batch][3][n]");
+    if (r && nr != per && nr != nx) return range_err(env, "ref must be one ciphertext [2][n] or the shape of ct");
+    job *j = job_new(&k, run_ct_square_scaled, NULL);
+    j->p[0] = x; j->p[1] = r; j->p[2] = o; j->v[0] = t; j->v[1] = r ? nr / per : 0; j->batch = nx / per;
+    napi_value keep[3] = {k.argv[1], k.argv[3], k.argv[2]};  /* a null ref is not kept */
+    return job_go(env, &k, j, k.argv[3], keep, r ? 3 : 2);
+}
+
 /* ctSquareRelinPrepared(ct, ref | null, rlkPrep [level][2][n], baseLog, out):
  * relinearize(ctSquare(ct, ref)), out [batch][2][n] (square_relin :1037-1055) */
 static int run_ct_square_relin(job *j) {
@@ -2048,6 +2142,9 @@ static napi_value init(napi_env env, napi_value exports) {
         M("relinearizePrepared", ctx_relin_prepared),
         M("ctSquare", ctx_ct_square),
         M("ctSquareRelinPrepared", ctx_ct_square_relin),
+        M("ctMultiplyScaled", ctx_ct_mul_scaled),
+        M("ctDotScaled", ctx_ct_dot_scaled),
+        M("ctSquareScaled", ctx_ct_square_scaled),
         M("blindRotate", ctx_blind_rotate),
         M("preparePublicKey", ctx_pk_prep),
         M("prepareSecretKey", ctx_sk_prep),
