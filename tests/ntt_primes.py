@@ -1,7 +1,7 @@
 """Moduli at the edges of the kernel families, and rows that fill the
 unreduced input windows (helpers of test_ntt_primes.py, test_gpu_ranges.py,
-test_gpu_ranges_stream.py and test_gpu_negacyclic.py; plain Python and numpy,
-no GPU).
+test_gpu_ranges_big.py, test_gpu_ranges_stream.py, test_gpu_negacyclic.py and
+test_gpu_rns_limbs.py; plain Python and numpy, no GPU).
 
 The library picks its kernels from the modulus
 (node-fhe-accelerate_amd/csrc/fhe_gpu.cpp, fhe_ctx_create):
@@ -136,6 +136,27 @@ SWEEP_NAMES = BOUNDARY_NAMES + ("wrap",)
 def sweep_primes(n: int) -> dict:
     """boundary_primes and the wrap prime: the moduli of the GPU sweeps."""
     return dict(boundary_primes(n), wrap=wrap_prime(n))
+
+
+LIMB_FAMILIES = ("lazy", "nonlazy32", "u64")
+
+
+def limb_families(n: int) -> dict:
+    """Three uniform RNS rings of three distinct primes each, one per kernel
+    shape of the one-launch limb kernels (fhe_rns_ctx_create: every limb of
+    the same word and laziness):
+
+    lazy       lazy_top, the next prime below it and the smallest prime
+               = 1 mod 2n: two neighbours at the bound and one whose constants
+               differ from theirs by orders of magnitude
+    nonlazy32  nonlazy_bottom, wrap, u32_top: 32-bit lanes, none lazy
+    u64        u64_bottom, the first prime above 2^45, u64_top"""
+    s = sweep_primes(n)
+    return {
+        "lazy": [s["lazy_top"], prime_below(s["lazy_top"] - 1, n), prime_above(1, n)],
+        "nonlazy32": [s["nonlazy_bottom"], s["wrap"], s["u32_top"]],
+        "u64": [s["u64_bottom"], prime_above(1 << 45, n), s["u64_top"]],
+    }
 
 
 # ---------------------------------------------------------------- adversarial rows

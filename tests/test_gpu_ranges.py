@@ -11,7 +11,9 @@ window.  The fused ciphertext kernels run on operands cut from those rows;
 squaring, the squared difference, partial decryption and the plaintext dot
 product at every degree, since their instantiations differ from one log2 N to
 the next.  (The streaming kernels' edges, around q = 2^63, are in
-test_gpu_ranges_stream.py.)
+test_gpu_ranges_stream.py; the two-pass degrees 32768 and 65536 in
+test_gpu_ranges_big.py, which runs check_window_rows and the fused bodies
+below.)
 
 Compat mode, bit-exact against the CPU oracle (oracle/ref_cpu.c).
 
@@ -64,7 +66,10 @@ def test_window_rows_benchmark_shape(fg):
     check_window_rows(fg, 16384, 132120577)
 
 
-def check_window_rows(fg, n, q):
+def check_window_rows(fg, n, q, tiles=4, ragged_for=None):
+    """tiles: how often the base rows repeat (and one row more below four);
+    ragged_for: the row count is no multiple of it (default: the polynomials
+    per workgroup)."""
     import torch
 
     r = fg.PolynomialRing(n, q)
@@ -73,13 +78,14 @@ def check_window_rows(fg, n, q):
     assert r.primitive_root == t.psi
     ppb = r.info.polys_per_block
     assert 1 <= ppb <= 256
+    ragged_for = ppb if ragged_for is None else ragged_for
 
     names, base = P.base_rows(n, q)
     inames, ibase = P.base_rows(n, q, inverse=True)
     # four tiles of the base rows (each meets every kind of second operand),
     # at least polys_per_block + 3 rows, never a whole number of workgroups
-    x = P.tile_rows(base, max(ppb + 3, 4 * len(names)), ppb)
-    xi = P.tile_rows(ibase, max(ppb + 3, len(inames)), ppb)
+    x = P.tile_rows(base, max(ppb + 3, tiles * len(names) + (tiles < 4)), ragged_for)
+    xi = P.tile_rows(ibase, max(ppb + 3, len(inames)), ragged_for)
     b = x.shape[0]
 
     got = r.forward_ntt(x)
@@ -150,29 +156,48 @@ class Ctx:
         return np.where(s == 2, np.uint64(self.q - 1), s).astype(np.uint64)
 
 
+def check_ct_multiply(c, x, others):
+    """x [b, 2, n] against each second operand of `others`, both domains."""
+    for y in others:
+        for is_ntt in (False, True):
+            got = c.eng.multiply(x, y, is_ntt=is_ntt)
+            for i in range(x.shape[0]):
+                assert (got[i] == c.ref.ct_multiply(x[i], y[i], is_ntt=is_ntt)).all(), (y is x, is_ntt, i)
+
+
+def check_relinearize(fg, c, ct3):
+    lv = 3 if c.q < 1 << 30 else 4
+    bl = digits(c.q, lv)
+    rlk = c.keys(11, lv, 2)
+    got = c.eng.relinearize(ct3, fg.EvaluationKey(c.ring, rlk, bl))
+    for i in range(ct3.shape[0]):
+        assert (got[i] == c.ref.relinearize(bl, lv, ct3[i], rlk)).all(), i
+
+
+def check_decrypt(fg, c, ct):
+    sk = c.ternary(19)
+    key = fg.SecretKey(c.ring, sk)
+    for is_ntt in (False, True):
+        res = c.eng.decrypt(ct, key, is_ntt=is_ntt, with_phase=True)
+        for i in range(ct.shape[0]):
+            ev, eph, emx = c.ref.decrypt(16, sk, ct[i], is_ntt)
+            assert (res.phase[i] == eph).all(), (is_ntt, i)
+            assert (res.values[i] == ev).all(), (is_ntt, i)
+            assert int(res.max_noise[i]) == emx, (is_ntt, i)
+
+
 @fused
 def test_fused_ct_multiply(fg, n, name):
     c = Ctx(fg, n, name)
     b = len(c.names)
     x = c.cts(b, 2)
-    for y in (c.cts(b, 2, shift=5), x):  # other rows, and the squares (lim-1 against lim-1)
-        for is_ntt in (False, True):
-            got = c.eng.multiply(x, y, is_ntt=is_ntt)
-            for i in range(b):
-                assert (got[i] == c.ref.ct_multiply(x[i], y[i], is_ntt=is_ntt)).all(), (y is x, is_ntt, i)
+    check_ct_multiply(c, x, (c.cts(b, 2, shift=5), x))  # other rows, and the squares (lim-1 against lim-1)
 
 
 @fused
 def test_fused_relinearize(fg, n, name):
     c = Ctx(fg, n, name)
-    b = len(c.names)
-    lv = 3 if c.q < 1 << 30 else 4
-    bl = digits(c.q, lv)
-    ct3 = c.cts(b, 3)
-    rlk = c.keys(11, lv, 2)
-    got = c.eng.relinearize(ct3, fg.EvaluationKey(c.ring, rlk, bl))
-    for i in range(b):
-        assert (got[i] == c.ref.relinearize(bl, lv, ct3[i], rlk)).all(), i
+    check_relinearize(fg, c, c.cts(len(c.names), 3))
 
 
 @fused
@@ -204,17 +229,7 @@ def test_fused_encrypt(fg, n, name):
 @pytest.mark.parametrize("comps", [2, 3])
 def test_fused_decrypt(fg, n, name, comps):
     c = Ctx(fg, n, name)
-    b = len(c.names)
-    sk = c.ternary(19)
-    key = fg.SecretKey(c.ring, sk)
-    ct = c.cts(b, comps)
-    for is_ntt in (False, True):
-        res = c.eng.decrypt(ct, key, is_ntt=is_ntt, with_phase=True)
-        for i in range(b):
-            ev, eph, emx = c.ref.decrypt(16, sk, ct[i], is_ntt)
-            assert (res.phase[i] == eph).all(), (is_ntt, i)
-            assert (res.values[i] == ev).all(), (is_ntt, i)
-            assert int(res.max_noise[i]) == emx, (is_ntt, i)
+    check_decrypt(fg, c, c.cts(len(c.names), comps))
 
 
 @fused
@@ -286,8 +301,12 @@ Q63 = 9223370937344327681     # just below 2^63: wide transforms with a true N^-
 # two ciphertexts.  At QG the compat N^-1 is the reference's 0 and every
 # coefficient-form result is all zeros (test_gpu_wide.py), so only the
 # NTT-domain results say anything there.
-COMPOSED = [(32768, P27), (1024, Q62), (1024, Q63), (1024, P.QG)]
+# P27 is past the lazy bound at 32768, so the lazy row kernel of ntt_big.hip
+# and the first 64-bit modulus at 65536 come in through BIG_COMPOSED.
+BIG_COMPOSED = [(32768, P.sweep_primes(32768)["lazy_top"]), (65536, P.sweep_primes(65536)["u64_bottom"])]
+COMPOSED = [(32768, P27), (1024, Q62), (1024, Q63), (1024, P.QG)] + BIG_COMPOSED
 composed = pytest.mark.parametrize("n,q", COMPOSED)
+COEFF_COMPOSED = [nq for nq in COMPOSED if nq[1] != P.QG]  # coefficient-form results: not at QG
 
 
 def domains(q):
@@ -560,7 +579,7 @@ def test_composed_square(fg, n, q):
     check_squared_difference(c, few=True)
 
 
-@pytest.mark.parametrize("n,q", COMPOSED[:3])  # coefficient-form results: not at QG
+@pytest.mark.parametrize("n,q", COEFF_COMPOSED)
 def test_composed_square_relin_and_partial_decrypt(fg, n, q):
     c = Ctx(fg, n, q)
     check_square_relin(fg, c, few=True)

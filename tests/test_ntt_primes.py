@@ -114,6 +114,61 @@ def test_oracle_accepts_boundary_primes(logn):
             assert (t.inverse(t.forward(x)) == x).all(), (logn, name)
 
 
+@pytest.mark.parametrize("logn,bound", [(15, 126322567), (16, 119304647)])
+def test_two_pass_degrees_premise(logn, bound):
+    """The premise of test_gpu_ranges_big.py: at N = 32768 / 65536 the usual
+    27-bit prime is past the lazy bound, so only lazy_top reaches the lazy row
+    kernel of ntt_big.hip; the six sweep primes exist, fall on the stated sides
+    and have the word sizes test_window_rows_vs_oracle states."""
+    n = 1 << logn
+    assert P.lazy_bound(n) == bound and (1 << 32) // (4 + 2 * logn) == bound
+    s = P.sweep_primes(n)
+    assert tuple(s) == P.SWEEP_NAMES and len(set(s.values())) == 6
+    for name, q in s.items():
+        assert P.is_prime(q) and q % (2 * n) == 1, (logn, name)
+        assert P.word_bits(q) == (64 if name in ("u64_bottom", "u64_top") else 32), (logn, name)
+        assert P.is_lazy(n, q) == (name == "lazy_top"), (logn, name)
+        assert pow(oracle.NTT(n, q).psi, n, q) == q - 1, (logn, name)
+    assert s["lazy_top"] <= bound < s["nonlazy_bottom"] < s["wrap"] < s["u32_top"] < 1 << 30
+    assert 1 << 30 < s["u64_bottom"] < s["u64_top"] < T62
+    assert (3 + logn) * s["wrap"] - 1 >= 1 << 32
+    p27 = 132120577
+    assert p27 % (2 * n) == 1 and p27 > bound and not P.is_lazy(n, p27) and P.word_bits(p27) == 32
+    assert P.is_lazy(16384, p27)  # (it is lazy at the largest fused degree)
+
+
+@pytest.mark.parametrize("logn", range(2, 15))
+def test_limb_families(logn):
+    """Three rings of three distinct NTT primes, every limb of a ring in the
+    same kernel family (word and laziness), so that fhe_rns_ctx_create takes
+    the one-launch path for each."""
+    n = 1 << logn
+    fam = P.limb_families(n)
+    s = P.sweep_primes(n)
+    assert tuple(fam) == P.LIMB_FAMILIES
+    for name, ring in fam.items():
+        assert len(ring) == 3 and len(set(ring)) == 3, (logn, name)
+        for q in ring:
+            assert P.is_prime(q) and q % (2 * n) == 1 and q < T62, (logn, name, q)
+    assert all(P.is_lazy(n, q) and P.word_bits(q) == 32 for q in fam["lazy"])
+    assert all(not P.is_lazy(n, q) and P.word_bits(q) == 32 for q in fam["nonlazy32"])
+    assert all(not P.is_lazy(n, q) and P.word_bits(q) == 64 for q in fam["u64"])
+    top, below, least = fam["lazy"]
+    assert top == s["lazy_top"] and below < top and P.prime_above(below, n) == top
+    assert not any(P.is_prime(c) for c in range(2 * n + 1, least, 2 * n)) and least < 1 << 20 < below
+    assert fam["nonlazy32"] == [s["nonlazy_bottom"], s["wrap"], s["u32_top"]]
+    lo, mid, hi = fam["u64"]
+    assert (lo, hi) == (s["u64_bottom"], s["u64_top"]) and lo < 1 << 45 < mid < hi
+    assert not any(P.is_prime(c) for c in range(mid - 2 * n, 1 << 45, -2 * n))
+
+
+def test_pinned_limb_families():
+    assert P.limb_families(16)["lazy"] == [357913921, 357913793, 97]
+    f = P.limb_families(16384)
+    assert f["lazy"] == [133857281, 132710401, 65537]
+    assert f["nonlazy32"] == [134250497, 253001729, 1073643521]
+
+
 @pytest.mark.parametrize("n,q", [(4, 536870849), (8, 17), (16, 97), (64, 268437889), (1024, 1073707009),
                                  (1024, T62 - 22527)])
 @pytest.mark.parametrize("inverse", [False, True])
