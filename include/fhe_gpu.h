@@ -387,6 +387,94 @@ int fhe_ct_dot_scaled_batch(fhe_scale_ctx *sc, const uint64_t *a, const uint64_t
 /* square(ct - ref), ref / ref_count as fhe_ct_square_batch */
 int fhe_ct_square_scaled_batch(fhe_scale_ctx *sc, const uint64_t *ct, const uint64_t *ref, size_t ref_count, uint64_t *out, size_t batch, int where);
 
+/* ---- SIMD batching: slot encode / decode, slot rotations, slot sums -------
+ * CRT batching of BFV plaintexts.  (No reference counterpart: its "packed"
+ * plaintext writes values into coefficients.)  n a power of two >= 4, t odd
+ * with t = 1 (mod 2n), psi the primitive 2n-th root that a negacyclic context
+ * (n, t) reports (fhe_ctx_info.psi; fhe_simd_info.psi).
+ *
+ * Slots.  n slots in 2 rows of n/2 columns, s = r n/2 + i.  Exponent e(s) =
+ *   3^i mod 2n for r = 0 and 2n - (3^i mod 2n) for r = 1 (every odd residue
+ *   below 2n exactly once); transform index k(s) = (e(s) - 1) / 2, the table
+ *   fhe_simd_slot_index returns (host [n]).
+ * encode.  X[k(s)] = values[s] mod t; out = the words of fhe_ntt_inv_batch on
+ *   the negacyclic context (n, t) applied to X, canonical in [0, t): the
+ *   polynomial with out(psi^e(s)) = values[s].  With lift != 0 each word c is
+ *   returned as its centred representative mod q: c when c <= (t - 1) / 2,
+ *   else q - (t - c) -- the form multiply_plain / fhe_ct_dot_plain_batch want;
+ *   lift == 0 is the form fhe_encrypt_batch / fhe_add_plain_batch take as
+ *   `values`.  Input words are any u64, read mod t.
+ * decode.  out[s] = Y[k(s)], Y the words of fhe_ntt_fwd_batch on that context
+ *   applied to the input (any u64, read mod t): the `values` output of
+ *   fhe_decrypt_batch / fhe_combine_partials_batch.
+ * The slot-wise meaning assumes a prime t: t is not tested for primality, and
+ *   for a composite t that passes the inner context's checks the words are
+ *   still the ones defined above.  Ring products of encodings decode to
+ *   slot-wise products mod t, sums to slot-wise sums.
+ * Rotation element.  g(steps, swap) = 3^(steps mod n/2) (2n - 1)^swap mod 2n
+ *   (fhe_simd_rotation_element: pure host arithmetic, no GPU; steps is signed,
+ *   a negative value rotates right; FHE_ERR_INVALID_ARG for n not a power of
+ *   two in [4, 65536] or a null g).  If m encodes v, sigma_g(m)
+ *   (fhe_poly_galois_batch) decodes to w[r][i] = v[r xor swap][(i + steps)
+ *   mod n/2].
+ * Slot sum.  With g_i = 3^(2^i) mod 2n for i < log2(n/2), then g = 2n - 1
+ *   (log2 n elements in all), x <- x + sigma_{g_i}(x) over all of them leaves
+ *   sum_s v_s in every slot; without the last element each slot holds its
+ *   row's sum.  On ciphertexts this is fhe_ct_galois_chain_batch with
+ *   add_input = 1 (sum_slots).  Noise: every step doubles the noise and adds
+ *   one key switch, so log2 n steps cost about n x the input noise.  At
+ *   t = 65537 with a 62-bit q and a 2^16 x 4 key-switch base the slot sum
+ *   after a scaled product has a margin of only 8 - 17 at n = 64 and no longer
+ *   decodes at n = 256: sum_slots after a multiplication needs a small t
+ *   (t = 257 leaves a margin above 10^7 there) or a finer key-switch base.
+ * These are SIMD slots.  The "slot" of fhe_slot_extract_batch,
+ *   fhe_lwe_pack_batch and the slot-isolating trace is a COEFFICIENT index:
+ *   fhe_ct_trace_batch keeps coefficients, not SIMD slots, and a packed
+ *   comparison bit sits at a coefficient.
+ *
+ * fhe_simd_ctx_create mirrors fhe_scale_ctx_create: it BORROWS ctx (n, device,
+ *   q for `lift`, and the stream, followed at every call) and must be
+ *   destroyed before ctx.  It owns a negacyclic context (n, t) on the same
+ *   device and the two index tables on the device.  Errors: "null out" / "null
+ *   context" before anything else; FHE_ERR_UNSUPPORTED for a compat or a
+ *   multi-device ctx; FHE_ERR_INVALID_ARG for t < 3 or t >= q; otherwise
+ *   whatever the inner fhe_ctx_create(n, t) answers (even t, t != 1 mod 2n, no
+ *   root), code and message unchanged.
+ * fhe_simd_encode_batch / fhe_simd_decode_batch: buffers [batch][n], out of
+ *   place (overlap: FHE_ERR_INVALID_ARG).  A null buffer and batch == 0 are
+ *   checked before the context is looked at ("null buffer", "at least one
+ *   polynomial is needed", then "null simd context").  Device buffers must be
+ *   16-byte aligned; FHE_HOST stages chunk by chunk.  Every n the context
+ *   takes and every t: n <= 16384 and t < 2^62 run one fused kernel (the
+ *   permutation is part of the transform's load / store; 32-bit lanes for t <
+ *   2^30); n > 16384 or t >= 2^62 run composed -- a permutation kernel and the
+ *   batched transforms through one stream-ordered temporary of at most 1 GiB
+ *   per chunk, no host synchronisation -- with bit-identical words.
+ *   FHE_SIMD_FUSED=0 (read per call) forces the composed path.
+ * fhe_ct_galois_chain_batch: x_0 = ct, x_{i+1} = fhe_ct_galois_batch(g =
+ *   gs[i], key block key_idx ? key_idx[i] : i of swk_ntt [nkeys][level][2][n],
+ *   x_i, add_input) for i < nsteps, out = x_nsteps: word-identical to that
+ *   chain of calls.  gs / key_idx are HOST arrays in both residences, copied
+ *   before the call returns.  Every context fhe_ct_galois_batch takes, a
+ *   multi-device one (splits the batch) and FHE_HOST included; the steps
+ *   ping-pong between out and one stream-ordered temporary without a host
+ *   synchronisation.  add_input = 0 composes rotations, add_input = 1 is
+ *   rotate-and-sum.  Errors: fhe_ct_galois_batch's own; nsteps == 0 or nsteps
+ *   > 64: "steps must be between 1 and 64"; a null gs; every g is checked
+ *   (odd, then range) before any launch. */
+typedef struct fhe_simd_ctx fhe_simd_ctx;
+typedef struct { uint64_t q, t, psi; uint32_t n; int32_t word_bits; } fhe_simd_info;   /* 32 bytes */
+int fhe_simd_ctx_create(fhe_ctx *ctx, uint64_t t, fhe_simd_ctx **out);
+void fhe_simd_ctx_destroy(fhe_simd_ctx *sc);
+int fhe_simd_ctx_get_info(const fhe_simd_ctx *sc, fhe_simd_info *info);
+int fhe_simd_slot_index(const fhe_simd_ctx *sc, uint32_t *index);          /* host [n]: k(s) */
+int fhe_simd_rotation_element(uint32_t n, int64_t steps, int swap_rows, uint32_t *g);   /* host only, no GPU */
+int fhe_simd_encode_batch(fhe_simd_ctx *sc, const uint64_t *values, int lift, uint64_t *out, size_t batch, int where);
+int fhe_simd_decode_batch(fhe_simd_ctx *sc, const uint64_t *in, uint64_t *out, size_t batch, int where);
+int fhe_ct_galois_chain_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, uint32_t nsteps, const uint32_t *gs,
+                              const uint32_t *key_idx, const uint64_t *swk_ntt, const uint64_t *ct, int add_input,
+                              uint64_t *out, size_t batch, int where);
+
 /* ---- ciphertext tally (encryption.cpp:1061-1067, 1153-1168, 1327-1460) ---
  * EncryptionEngine::batch_add / batch_add_tree / tally_votes /
  * tally_multi_candidate: the sum of `count` ciphertexts of `polys` (1..3)

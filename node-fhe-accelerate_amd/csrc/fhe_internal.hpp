@@ -356,4 +356,19 @@ hipError_t launch_center_lift(const ScaleConsts &k, const uint64_t *in, const ui
 hipError_t launch_scale_round(const ScaleConsts &k, const uint64_t *xq, const uint64_t *x1, const uint64_t *x2,
                               uint64_t *out, size_t words, hipStream_t s);
 
+// SIMD (CRT batching) codec (simd_codec.hip).  tp is the plan of the negacyclic
+// context (n, t); slot_at [n] (device) maps transform index k to the slot s
+// with k(s) = k.  The fused family only (n <= 16384, t < 2^62).
+//   encode: out = inv(X), X[k] = values[slot_at[k]] mod t; a word above `half`
+//     comes back plus lift_add (q - t for the centred lift mod q, 0 for none).
+//   decode: out[slot_at[k]] = fwd(in)[k].
+hipError_t launch_simd_encode(const Plan &tp, const uint32_t *slot_at, const uint64_t *values, uint64_t half,
+                              uint64_t lift_add, uint64_t *out, size_t batch);
+hipError_t launch_simd_decode(const Plan &tp, const uint32_t *slot_at, const uint64_t *in, uint64_t *out, size_t batch);
+// Composed path, any n = 2^logn and odd t: out[i] = in[tab[i]] mod t per row
+// (tab [n], device), and the centred lift of canonical words in place.
+hipError_t launch_simd_permute(const ModConsts &m, uint32_t logn, const uint32_t *tab, const uint64_t *in, uint64_t *out,
+                               size_t npoly, hipStream_t s);
+hipError_t launch_simd_lift(uint64_t half, uint64_t lift_add, uint64_t *x, size_t words, hipStream_t s);
+
 }  // namespace FHE_NS

@@ -92,6 +92,12 @@ class ScaleInfo(C.Structure):
     ]
 
 
+class SimdInfo(C.Structure):
+    _fields_ = [
+        ("q", C.c_uint64), ("t", C.c_uint64), ("psi", C.c_uint64), ("n", C.c_uint32), ("word_bits", C.c_int32),
+    ]
+
+
 u64p = C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
@@ -164,6 +170,16 @@ SIGNATURES = [
     ("fhe_ct_multiply_scaled_batch", C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_ct_dot_scaled_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int]),
     ("fhe_ct_square_scaled_batch", C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int]),
+    ("fhe_simd_ctx_create", C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
+    ("fhe_simd_ctx_destroy", None, [vp]),
+    ("fhe_simd_ctx_get_info", C.c_int, [vp, C.POINTER(SimdInfo)]),
+    ("fhe_simd_slot_index", C.c_int, [vp, C.POINTER(C.c_uint32)]),
+    ("fhe_simd_rotation_element", C.c_int, [C.c_uint32, C.c_int64, C.c_int, C.POINTER(C.c_uint32)]),
+    ("fhe_simd_encode_batch", C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.c_int]),
+    ("fhe_simd_decode_batch", C.c_int, [vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_galois_chain_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, C.c_int, vp,
+      C.c_size_t, C.c_int]),
     ("fhe_glwe_rotate_batch", C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_cmux_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_blind_rotate_batch", C.c_int,
@@ -1092,6 +1108,20 @@ class KeyGenerator:
             self.switch_key(s, s, base_log, level, stream + 2 * level * i, g, out=out[i])
         return SwitchKey(r, out, base_log, level, gs)
 
+    def rotation_keys(self, sk, base_log: int, level: int, stream: int):
+        """The Galois keys of the SIMD slot rotations in one buffer
+        [log2 n, level, 2, n]: key i < log2(n/2) for g_i = 3^(2^i) mod 2n (rotate
+        the rows left by 2^i), the last one for g = 2n - 1 (swap the rows) --
+        the slot-sum list of include/fhe_gpu.h.  Key i on streams
+        stream + 2 level i ..., as galois_keys."""
+        r = self.ring
+        s = _as_u64(sk.poly if isinstance(sk, SecretKey) else sk)
+        gs = slot_sum_elements(r.degree)
+        out = _empty(s, (len(gs), level, 2, r.degree))
+        for i, g in enumerate(gs):
+            self.switch_key(s, s, base_log, level, stream + 2 * level * i, g, out=out[i])
+        return SwitchKey(r, out, base_log, level, gs)
+
     def threshold_keys(self, threshold: int, total_shares: int, stream: int, device_out: bool = False):
         """generate_threshold_keys (:479-546): a ternary master key from
         ``stream``, the random sharing polynomial j (1 <= j < threshold) from
@@ -1338,6 +1368,97 @@ class ScaledMultiplier:
 
     def square(self, ct, out=None):
         return self.squared_difference(ct, None, out)
+
+
+def rotation_element(n: int, steps: int, swap: bool = False) -> int:
+    """g(steps, swap) = 3^(steps mod n/2) (2n - 1)^swap mod 2n
+    (fhe_simd_rotation_element; host arithmetic, no GPU): sigma_g rotates both
+    slot rows left by `steps` (negative: right) and swaps them with `swap`."""
+    g = C.c_uint32()
+    _check(lib().fhe_simd_rotation_element(int(n), int(steps), int(bool(swap)), C.byref(g)))
+    return int(g.value)
+
+
+def slot_sum_elements(n: int):
+    """The Galois elements of the slot sum: 3^(2^i) mod 2n for i < log2(n/2),
+    then 2n - 1 (log2 n elements)."""
+    return [pow(3, 1 << i, 2 * n) for i in range((n // 2).bit_length() - 1)] + [2 * n - 1]
+
+
+class SimdEncoder:
+    """CRT batching (fhe_simd_ctx): n values mod t <-> the plaintext
+    polynomial whose evaluations at the 2n-th roots of unity mod t they are,
+    so that ring products act slot by slot and the Galois automorphisms
+    rotate the slots.  Negacyclic single-device rings, t = 1 mod 2n.  Owns the
+    context (an (n, t) transform context and two index tables on the ring's
+    device); it borrows ``ring`` and keeps it alive."""
+
+    def __init__(self, ring: "PolynomialRing", t: int):
+        self._h = None
+        h = C.c_void_p()
+        _check(lib().fhe_simd_ctx_create(ring._h, int(t), C.byref(h)))
+        self._h = h
+        self.ring = ring
+        si = SimdInfo()
+        _check(lib().fhe_simd_ctx_get_info(h, C.byref(si)))
+        self.info = {"q": int(si.q), "t": int(si.t), "psi": int(si.psi), "n": int(si.n), "wordBits": int(si.word_bits)}
+        self.t = int(si.t)
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib is not None:
+            _lib.fhe_simd_ctx_destroy(h)
+        self._h = None
+
+    __del__ = close
+
+    def slot_index(self):
+        """k(s): the transform index of slot s, [n] uint32."""
+        idx = np.empty(self.ring.degree, dtype=np.uint32)
+        _check(lib().fhe_simd_slot_index(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return idx
+
+    def _rows(self, values):
+        """[..., n] u64 rows; a short last axis is zero-padded to n (as EncryptionEngine._slots)."""
+        n = self.ring.degree
+        if _is_tensor(values):
+            v = values if values.dim() else values.reshape(1)
+            if v.shape[-1] != n:
+                pad = torch.zeros(tuple(v.shape[:-1]) + (n,), dtype=v.dtype, device=v.device)
+                pad[..., : min(n, v.shape[-1])] = v[..., :n]
+                v = pad
+            return v.contiguous()
+        v = np.asarray(values, dtype=np.uint64)
+        v = v.reshape(1) if v.ndim == 0 else v
+        if v.shape[-1] != n:
+            pad = np.zeros(tuple(v.shape[:-1]) + (n,), dtype=np.uint64)
+            pad[..., : min(n, v.shape[-1])] = v[..., :n]
+            v = pad
+        return np.ascontiguousarray(v)
+
+    def _run(self, fn, x, out, args_of):
+        r = self.ring
+        nb = r._batch(x)
+        out = _like(x) if out is None else out
+        bi, bo = _Buf(x), _Buf(out, True)
+        if bo.count != bi.count:
+            raise FHEError(-9, "output shape differs from the input")
+        w = _where(bi, bo)
+        r._bind_stream(w)
+        _check(fn(*args_of(bi.ptr, bo.ptr, nb, w)))
+        return out
+
+    def encode(self, values, lift: bool = False, out=None):
+        """Slot values [..., n] (any u64, read mod t; fewer are zero-padded)
+        -> plaintext polynomials [..., n] in [0, t); with lift, as centred
+        representatives mod q (the form multiply_plain / dot_plain take)."""
+        return self._run(lib().fhe_simd_encode_batch, self._rows(values), out,
+                         lambda i, o, nb, w: (self._h, i, int(bool(lift)), o, nb, w))
+
+    def decode(self, polys, out=None):
+        """Plaintext polynomials [..., n] (any u64, read mod t) -> slot values."""
+        return self._run(lib().fhe_simd_decode_batch, _as_u64(polys), out,
+                         lambda i, o, nb, w: (self._h, i, o, nb, w))
 
 
 class EncryptionEngine:
@@ -2008,6 +2129,93 @@ class EncryptionEngine:
         x = rot.multiply_glwe_by_monomial(ct, [-slot] * nb)
         y = self.trace(x, keys)
         return rot.multiply_glwe_by_monomial(y, [slot] * nb, out=x if out is None else out)
+
+    # -- SIMD batching (SimdEncoder with this engine's t): slot-wise products, slot rotations and slot
+    # sums.  These are SIMD slots; isolate_slot / slot_extract / pack_lwe address coefficients.
+    @property
+    def simd(self) -> "SimdEncoder":
+        if getattr(self, "_simd", None) is None:
+            self._simd = SimdEncoder(self.ring, self.t or 4)
+        return self._simd
+
+    def encode_simd(self, values, lift: bool = False, out=None):
+        """Slot values -> the plaintext polynomial encrypt() / add_plain() take as `values`."""
+        return self.simd.encode(values, lift, out)
+
+    def decode_simd(self, polys, out=None):
+        return self.simd.decode(polys, out)
+
+    def decrypt_simd(self, ct, sk: SecretKey):
+        """decrypt, then decode: a DecryptionResult whose values are the slot values."""
+        res = self.decrypt(ct, sk)
+        res.values = self.simd.decode(res.values)
+        return res
+
+    def galois_chain(self, ct, gs, keys: "SwitchKey", key_idx=None, add_input: bool = False, out=None):
+        """fhe_ct_galois_chain_batch: x <- apply_galois(gs[i], key key_idx[i]
+        (default i) of `keys` [nkeys, level, 2, n], x, add_input) for every i in
+        one call, word for word that chain of calls."""
+        r = self.ring
+        if keys.steps is None:
+            raise FHEError(-9, "galois_chain needs keys [nkeys, level, 2, n]")
+        gs = [int(g) for g in gs]
+        idx = list(range(len(gs))) if key_idx is None else [int(k) for k in key_idx]
+        if len(idx) != len(gs):
+            raise FHEError(-9, "gs and key_idx must have the same length")
+        if any(k < 0 or k >= keys.steps for k in idx):
+            raise FHEError(-9, "key index out of range")
+        if any(g < 0 or g >= 1 << 32 for g in gs):
+            raise FHEError(-9, "Galois element out of range")
+        ct = _as_u64(ct)
+        nb = _lead(ct, (2, r.degree))
+        out = _like(ct) if out is None else out
+        bi, bo = _Buf(ct), _Buf(out, True)
+        bk = _Buf(keys.key_ntt) if keys.level else None
+        w = _where(bi, bk, bo)
+        r._bind_stream(w)
+        ns = len(gs)
+        _check(lib().fhe_ct_galois_chain_batch(r._h, keys.base_log, keys.level, ns, (C.c_uint32 * max(1, ns))(*gs),
+                                               (C.c_uint32 * max(1, ns))(*idx), bk.ptr if bk else None, bi.ptr,
+                                               int(bool(add_input)), bo.ptr, nb, w))
+        return out
+
+    def _rotation_keys(self, keys):
+        n = self.ring.degree
+        if keys.steps is None or list(keys.g) != slot_sum_elements(n):
+            raise FHEError(-9, "needs the keys of KeyGenerator.rotation_keys")
+
+    def rotate_rows(self, ct, steps: int, keys: "SwitchKey", out=None):
+        """Both slot rows rotated left by `steps` (negative: right): the
+        binary decomposition of steps mod n/2 over the power-of-two keys, one
+        chain call.  A multiple of n/2 copies the reduced words."""
+        self._rotation_keys(keys)
+        n = self.ring.degree
+        m = int(steps) % (n // 2)
+        bits = [i for i in range((n // 2).bit_length() - 1) if (m >> i) & 1]
+        if not bits:
+            return self.ring.galois(_as_u64(ct), 1, out)
+        return self.galois_chain(ct, [keys.g[i] for i in bits], keys, bits, False, out)
+
+    def rotate_columns(self, ct, keys: "SwitchKey", out=None):
+        """The two slot rows swapped (sigma_{2n-1})."""
+        self._rotation_keys(keys)
+        last = keys.steps - 1
+        return self.galois_chain(ct, [keys.g[last]], keys, [last], False, out)
+
+    def sum_slots(self, ct, keys: "SwitchKey", rows_only: bool = False, out=None):
+        """sum_s v_s in every slot (rows_only: each slot its row's sum):
+        x <- x + sigma_g(x) over the keys.  Every step doubles the noise and
+        adds one key switch; see include/fhe_gpu.h for the limit at t = 65537."""
+        self._rotation_keys(keys)
+        ns = keys.steps - 1 if rows_only else keys.steps
+        if ns == 0:
+            return self.ring.galois(_as_u64(ct), 1, out)
+        return self.galois_chain(ct, list(keys.g[:ns]), keys, None, True, out)
+
+    def inner_product_scaled(self, ct1, ct2, ek: EvaluationKey, keys: "SwitchKey", out=None):
+        """<v, w> mod t in every slot of SIMD-encoded encryptions of v and w:
+        multiply_scaled -> relinearize -> sum_slots."""
+        return self.sum_slots(self.multiply_relin_scaled(ct1, ct2, ek), keys, False, out)
 
 
 class BootstrapEngine:

@@ -381,6 +381,32 @@ export interface FHEScaledEngine extends FHEGaloisEngine {
     progress?: ProgressCallback, options?: TallyWeightedOptions): Promise<Ciphertext>;
 }
 
+/** The Galois keys of the slot rotations (generateRotationKeys): log2(n) keys, for the row
+ * rotations by 2^i and the row swap. */
+export interface RotationKeys {
+  readonly __brand: 'RotationKeys';
+  readonly handle: bigint;
+  readonly keyId: bigint;
+  readonly steps: number;
+  readonly decompBaseLog: number;
+  readonly decompLevel: number;
+}
+
+/** SIMD batching (fhe_simd_encode_batch, fhe_simd_decode_batch, fhe_ct_galois_chain_batch): with
+ * plaintextModulus = 1 mod 2 polyDegree a plaintext holds polyDegree slot values in 2 rows;
+ * products of encodings act slot by slot, rotateRows / rotateColumns move the slots and sumSlots
+ * leaves their sum in every slot.  These are SIMD slots: isolateSlot and packBits address
+ * coefficients.  Mode 'negacyclic', coefficient form, single device. */
+export interface FHESimdEngine extends FHEScaledEngine {
+  generateRotationKeys(sk: SecretKey, options?: PackKeyOptions): Promise<RotationKeys>;
+  encodeSimd(values: bigint[], options?: { lift?: boolean }): Promise<Plaintext>;
+  decodeSimd(plaintext: Plaintext | bigint[]): Promise<bigint[]>;
+  rotateRows(ct: Ciphertext, steps: number, keys: RotationKeys): Promise<Ciphertext>;
+  rotateColumns(ct: Ciphertext, keys: RotationKeys): Promise<Ciphertext>;
+  sumSlots(ct: Ciphertext, keys: RotationKeys, options?: { rowsOnly?: boolean }): Promise<Ciphertext>;
+  innerProductScaled(ct1: Ciphertext, ct2: Ciphertext, ek: EvaluationKey, keys: RotationKeys): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -462,6 +488,13 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   multiplyScaled(ct1: Ciphertext, ct2: Ciphertext): Promise<Ciphertext>;
   dotProductScaled(cts1: Ciphertext[], cts2: Ciphertext[], progress?: ProgressCallback): Promise<Ciphertext>;
   squareScaled(ct: Ciphertext): Promise<Ciphertext>;
+  generateRotationKeys(sk: SecretKey, options?: PackKeyOptions): Promise<RotationKeys>;
+  encodeSimd(values: bigint[], options?: { lift?: boolean }): Promise<Plaintext>;
+  decodeSimd(plaintext: Plaintext | bigint[]): Promise<bigint[]>;
+  rotateRows(ct: Ciphertext, steps: number, keys: RotationKeys): Promise<Ciphertext>;
+  rotateColumns(ct: Ciphertext, keys: RotationKeys): Promise<Ciphertext>;
+  sumSlots(ct: Ciphertext, keys: RotationKeys, options?: { rowsOnly?: boolean }): Promise<Ciphertext>;
+  innerProductScaled(ct1: Ciphertext, ct2: Ciphertext, ek: EvaluationKey, keys: RotationKeys): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension); part names another
    * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
   deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
@@ -605,6 +638,14 @@ export declare class NttContext {
    * g_i = n / 2^i + 1 (fhe_ct_trace_batch). */
   ctTrace(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Words;
   ctTraceAsync(baseLog: number, steps: number, keysPrep: Words, ct: Words, out: Words): Promise<Words>;
+  /** fhe_simd_encode_batch / fhe_simd_decode_batch with the codec context of plaintext modulus t */
+  simdEncode(t: bigint | number, values: Words, lift: number, out: Words): Words;
+  simdEncodeAsync(t: bigint | number, values: Words, lift: number, out: Words): Promise<Words>;
+  simdDecode(t: bigint | number, polys: Words, out: Words): Words;
+  simdDecodeAsync(t: bigint | number, polys: Words, out: Words): Promise<Words>;
+  /** fhe_ct_galois_chain_batch: x <- ctGalois(gs[i], key keyIdx[i] of keysPrep, x, addInput) for every i */
+  ctGaloisChain(baseLog: number, level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ct: Words, addInput: number, out: Words): Words;
+  ctGaloisChainAsync(baseLog: number, level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ct: Words, addInput: number, out: Words): Promise<Words>;
   /** Scale-invariant products round(t/q (ct1 (x) ct2)) (t: plaintext modulus, 0 selects 4); the
    * context keeps one scale context per t.  ct [batch][2][n] -> out [batch][3][n] */
   ctMultiplyScaled(t: bigint | number, ct1: Words, ct2: Words, out: Words): Words;

@@ -1419,6 +1419,112 @@ function makeEngineClass(native) {
       });
     }
 
+    // ---- SIMD batching (fhe_simd_encode_batch, fhe_simd_decode_batch,
+    // fhe_ct_galois_chain_batch): n values mod t in the slots of one plaintext
+    // (t = 1 mod 2n), products slot by slot, slot rotations and slot sums.
+    // These are SIMD slots; isolateSlot / packBits address coefficients.
+    // Mode 'negacyclic', coefficient form, one device.
+    /** 3^(2^i) mod 2n for i < log2(n/2), then 2n - 1: row rotations by 2^i, then the row swap */
+    _slotSumElements() {
+      const n = this._n, gs = [];
+      let g = 3;
+      for (let i = 0; i < Math.log2(n / 2); i++) { gs.push(g); g = (g * g) % (2 * n); }
+      gs.push(2 * n - 1);
+      return gs;
+    }
+    _simdWords(values) {
+      if (!Array.isArray(values) || values.length > this._n) throw new FHEError('expected at most polyDegree slot values', FHEErrorCode.INVALID_PARAMETERS);
+      const w = new BigUint64Array(this._n);
+      values.forEach((v, i) => { w[i] = u64(v); });
+      return w;
+    }
+    /** Slot values (fewer than n are zero-padded) -> the packed plaintext whose encryption
+     *  multiplies, rotates and sums slot by slot; options.lift gives the centred form mod q */
+    async encodeSimd(values, options) {
+      this._check();
+      return guard(async () => {
+        const src = this._upload(this._simdWords(values)), out = this._buf(this._n);
+        await this._ctx.simdEncodeAsync(this._tEff, src, options && options.lift ? 1 : 0, out);
+        const words = out.download();
+        src.free();
+        out.free();
+        return this.createPackedPlaintext(Array.from(words));
+      });
+    }
+    /** The slot values of a packed plaintext (decryptPacked's values, or a DecryptionResult's plaintext) */
+    async decodeSimd(plaintext) {
+      this._check();
+      return guard(async () => {
+        const vals = Array.isArray(plaintext) ? plaintext : (plaintext && plaintext.values);
+        const src = this._upload(this._simdWords(vals)), out = this._buf(this._n);
+        await this._ctx.simdDecodeAsync(this._tEff, src, out);
+        const words = out.download();
+        src.free();
+        out.free();
+        return Array.from(words);
+      });
+    }
+    /** The Galois keys of rotateRows / rotateColumns / sumSlots in one buffer: log2(n) keys */
+    async generateRotationKeys(sk, options) {
+      this._check();
+      return guard(async () => {
+        const s = this._st(sk, 'SecretKey');
+        const n = this._n, gs = this._slotSumElements();
+        const { bl, lv } = this._switchDecomp(options);
+        const per = lv * 2 * n;
+        const raw = this._buf(gs.length * per), prep = this._buf(gs.length * per);
+        for (let i = 0; i < gs.length; i++) await this._switchKeyInto(s, s, gs[i], bl, lv, raw.view(i * per, per));
+        await this._ctx.prepareRelinKeyAsync(raw, prep);
+        raw.free();
+        return this._handle('RotationKeys', { keyId: sk.keyId, steps: gs.length, decompBaseLog: bl, decompLevel: lv },
+          { buf: prep, baseLog: bl, level: lv, gs });
+      });
+    }
+    async _galoisChain(ct, keys, idx, addInput) {
+      const a = this._rlwe(ct), k = this._st(keys, 'RotationKeys'), n = this._n;
+      if (this._mode !== 1) throw new FHEError('slot rotations need mode negacyclic', FHEErrorCode.INVALID_PARAMETERS);
+      if (a.comps !== 2 || ct.isNtt) throw new FHEError('slot rotations take degree-1 coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+      if (ct.keyId !== keys.keyId) throw new FHEError('Rotation keys do not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      const out = this._buf(2 * n);
+      if (idx.length === 0) {
+        await this._ctx.polyGaloisAsync(a.buf, 1, out);
+        return this._ct(out, ct.keyId, ct.noiseBudget, 1, { packed: true });
+      }
+      await this._ctx.ctGaloisChainAsync(k.baseLog, k.level, BigUint64Array.from(idx, (i) => BigInt(k.gs[i])),
+        BigUint64Array.from(idx, (i) => BigInt(i)), k.buf, a.buf, addInput ? 1 : 0, out);
+      return this._ct(out, ct.keyId, ct.noiseBudget - idx.length * (addInput ? 2 : 1), 1, { packed: true });
+    }
+    /** Both slot rows rotated left by `steps` (negative: right): one chain call over the
+     *  power-of-two keys of the binary digits of steps mod n/2 */
+    async rotateRows(ct, steps, keys) {
+      this._check();
+      return guard(async () => {
+        if (!Number.isInteger(steps)) throw new FHEError('steps must be an integer', FHEErrorCode.INVALID_PARAMETERS);
+        const half = this._n / 2, m = ((steps % half) + half) % half, idx = [];
+        for (let i = 0; i < Math.log2(half); i++) if ((m >> i) & 1) idx.push(i);
+        return this._galoisChain(ct, keys, idx, false);
+      });
+    }
+    /** The two slot rows swapped */
+    async rotateColumns(ct, keys) {
+      this._check();
+      return guard(async () => this._galoisChain(ct, keys, [Math.log2(this._n) - 1], false));
+    }
+    /** The sum of all slots in every slot (options.rowsOnly: each row's sum in its slots).
+     *  Every step doubles the noise: after a multiplication use a small t (include/fhe_gpu.h). */
+    async sumSlots(ct, keys, options) {
+      this._check();
+      return guard(async () => {
+        const steps = Math.log2(this._n) - (options && options.rowsOnly ? 1 : 0);
+        return this._galoisChain(ct, keys, Array.from({ length: steps }, (_, i) => i), true);
+      });
+    }
+    /** <v, w> mod t in every slot: multiplyScaled, relinearize, sumSlots */
+    async innerProductScaled(ct1, ct2, ek, keys) {
+      const prod = await this.relinearize(await this.multiplyScaled(ct1, ct2), ek);
+      return this.sumSlots(prod, keys);
+    }
+
     // ---- serialisation: binary = header words + the native words, checksum = SHA-256
     _serialize(kind, h, words, meta, opts) {
       const fmt = (opts && opts.format) || 'binary';

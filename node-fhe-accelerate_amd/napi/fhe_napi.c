@@ -305,10 +305,15 @@ typedef struct {
     fhe_scale_ctx *sc[MAXSCALE];
     uint64_t sc_t[MAXSCALE];
     int nsc;
+    /* SIMD codec contexts, kept the same way */
+    fhe_simd_ctx *sm[MAXSCALE];
+    uint64_t sm_t[MAXSCALE];
+    int nsm;
 } nctx;
 static void nctx_release(nctx *k) {
     if (--k->refs == 0) {
         for (int i = 0; i < k->nsc; ++i) fhe_scale_ctx_destroy(k->sc[i]); /* they borrow k->c */
+        for (int i = 0; i < k->nsm; ++i) fhe_simd_ctx_destroy(k->sm[i]);
         fhe_ctx_destroy(k->c);
         pthread_mutex_destroy(&k->mu);
         free(k);
@@ -1866,6 +1871,100 @@ static napi_value ctx_ct_trace(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[4], keep, 3);
 }
 
+/* ---- SIMD batching (fhe_simd_encode_batch, fhe_simd_decode_batch, fhe_ct_galois_chain_batch).  The
+ * codec context of plaintext modulus t is made on first use and kept with the context, as scale_of. */
+static int simd_of(job *j, uint64_t t, fhe_simd_ctx **out) {
+    nctx *k = j->k;
+    for (int i = 0; i < k->nsm; ++i)
+        if (k->sm_t[i] == t) return *out = k->sm[i], 0;
+    fhe_simd_ctx *sc = NULL;
+    int rc = fhe_simd_ctx_create(k->c, t, &sc);
+    if (rc) return rc;
+    if (k->nsm == MAXSCALE) {
+        rc = fhe_ctx_synchronize(k->c);
+        fhe_simd_ctx_destroy(k->sm[0]);
+        memmove(k->sm, k->sm + 1, (MAXSCALE - 1) * sizeof k->sm[0]);
+        memmove(k->sm_t, k->sm_t + 1, (MAXSCALE - 1) * sizeof k->sm_t[0]);
+        k->nsm--;
+    }
+    k->sm[k->nsm] = sc;
+    k->sm_t[k->nsm++] = t;
+    *out = sc;
+    return rc;
+}
+/* simdEncode(t, values [batch][n], lift, out [batch][n]): slot values -> plaintext polynomials */
+static int run_simd_encode(job *j) {
+    fhe_simd_ctx *sc;
+    int rc = simd_of(j, j->v[0], &sc);
+    return rc ? rc : fhe_simd_encode_batch(sc, j->p[0], (int)j->v[1], j->p[1], j->batch, j->where);
+}
+static napi_value ctx_simd_encode(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    uint64_t t, *x, lift, *o;
+    size_t nx, no;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &x, &nx) || num_arg(env, &k, 2, &lift) || arr_arg(env, &k, 3, &o, &no) ||
+        nx == 0 || nx % k.n || no != nx)
+        return bad_args(env, "simdEncode(t, values [batch*n], lift, out [batch*n])"), NULL;
+    job *j = job_new(&k, run_simd_encode, NULL);
+    j->p[0] = x; j->p[1] = o; j->v[0] = t; j->v[1] = lift ? 1 : 0; j->batch = nx / k.n;
+    napi_value keep[2] = {k.argv[1], k.argv[3]};
+    return job_go(env, &k, j, k.argv[3], keep, 2);
+}
+/* simdDecode(t, polys [batch][n], out [batch][n]): plaintext polynomials -> slot values */
+static int run_simd_decode(job *j) {
+    fhe_simd_ctx *sc;
+    int rc = simd_of(j, j->v[0], &sc);
+    return rc ? rc : fhe_simd_decode_batch(sc, j->p[0], j->p[1], j->batch, j->where);
+}
+static napi_value ctx_simd_decode(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 3, &k)) return NULL;
+    uint64_t t, *x, *o;
+    size_t nx, no;
+    if (num_arg(env, &k, 0, &t) || arr_arg(env, &k, 1, &x, &nx) || arr_arg(env, &k, 2, &o, &no) || nx == 0 || nx % k.n ||
+        no != nx)
+        return bad_args(env, "simdDecode(t, polys [batch*n], out [batch*n])"), NULL;
+    job *j = job_new(&k, run_simd_decode, NULL);
+    j->p[0] = x; j->p[1] = o; j->v[0] = t; j->batch = nx / k.n;
+    napi_value keep[2] = {k.argv[1], k.argv[2]};
+    return job_go(env, &k, j, k.argv[2], keep, 2);
+}
+/* ctGaloisChain(baseLog, level, gs, keyIdx (host BigUint64Arrays [steps]), keysPrep [nkeys][level][2][n],
+ * ct [batch][2][n], addInput, out [batch][2][n]): x <- ctGalois(gs[i], key keyIdx[i], x, addInput) for every i */
+static int run_ct_galois_chain(job *j) {
+    const uint32_t ns = (uint32_t)j->v[2], *g = (const uint32_t *)j->owned;
+    return fhe_ct_galois_chain_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], ns, g, g + ns, j->v[1] ? j->p[0] : NULL,
+                                     j->p[1], (int)j->v[3], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_galois_chain(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "ctGaloisChain(baseLog, level, gs (BigUint64Array), keyIdx (BigUint64Array), keysPrep [nkeys*level*2n], "
+        "ct [batch*2n], addInput, out [batch*2n])";
+    call k;
+    if (call_begin(env, info, 8, &k)) return NULL;
+    uint64_t bl, lv, *gs, *ki, *key, *ct, add, *o;
+    size_t ng, nki, nk, nc, no;
+    if (num_arg(env, &k, 0, &bl) || num_arg(env, &k, 1, &lv) || k.argc < 4 || get_u64_array(env, k.argv[2], &gs, &ng) ||
+        get_u64_array(env, k.argv[3], &ki, &nki) || arr_arg(env, &k, 4, &key, &nk) || arr_arg(env, &k, 5, &ct, &nc) ||
+        num_arg(env, &k, 6, &add) || arr_arg(env, &k, 7, &o, &no) || ng == 0 || ng > 64 || nki != ng)
+        return bad_args(env, usage), NULL;
+    if (nc == 0 || nc % (2 * k.n) || no != nc) return range_err(env, "ct [batch][2][n], out [batch][2][n]");
+    const size_t per = lv * 2 * k.n;
+    for (size_t i = 0; i < ng; ++i)
+        if (gs[i] >> 32 || (per ? (ki[i] + 1) * per > nk : ki[i] != 0)) return range_err(env, "Galois element or key index out of range");
+    job *j = job_new(&k, run_ct_galois_chain, NULL);
+    j->owned = (uint64_t *)malloc(2 * ng * 4 + 8);
+    for (size_t i = 0; i < ng; ++i) {
+        ((uint32_t *)j->owned)[i] = (uint32_t)gs[i];
+        ((uint32_t *)j->owned)[ng + i] = (uint32_t)ki[i];
+    }
+    j->p[0] = key; j->p[1] = ct; j->p[2] = o;
+    j->v[0] = bl; j->v[1] = lv; j->v[2] = ng; j->v[3] = add ? 1 : 0; j->batch = nc / (2 * k.n);
+    napi_value keep[3] = {k.argv[4], k.argv[5], k.argv[7]};
+    return job_go(env, &k, j, k.argv[7], keep, 3);
+}
+
 /* ---- randomness and key material (fhe_sample_batch, fhe_*_generate) ---- */
 /* sample(kind, seed, stream, noiseStd, out) */
 static int run_sample(job *j) {
@@ -2167,6 +2266,9 @@ static napi_value init(napi_env env, napi_value exports) {
         M("polyGalois", ctx_poly_galois),
         M("ctGalois", ctx_ct_galois),
         M("ctTrace", ctx_ct_trace),
+        M("simdEncode", ctx_simd_encode),
+        M("simdDecode", ctx_simd_decode),
+        M("ctGaloisChain", ctx_ct_galois_chain),
         M("switchKeyGenerate", ctx_swk_gen),
         M("sample", ctx_sample),
         M("publicKeyGenerate", ctx_pk_gen),
