@@ -475,6 +475,88 @@ int fhe_ct_galois_chain_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, u
                               const uint32_t *key_idx, const uint64_t *swk_ntt, const uint64_t *ct, int add_input,
                               uint64_t *out, size_t batch, int where);
 
+/* ---- hoisted rotations and the plaintext linear transform -----------------
+ * Many rotations of ONE ciphertext, and sum_r p_r (*) rot_r(ct) for plaintext
+ * polynomials p_r (a plaintext matrix applied to a packed encrypted vector, one
+ * term per diagonal).  (No reference counterpart.)  The ciphertext is
+ * decomposed and transformed once; every automorphism then acts on spectra.
+ * In the negacyclic transform X_k = a(psi^(2k+1)), natural order, and sigma_g
+ * is the index map pi_g(k) = (((2k+1) g mod 2n) - 1) / 2 = g k + (g - 1) / 2
+ * mod n: fwd(sigma_g(a))[k] = fwd(a)[pi_g(k)], no sign and no arithmetic.
+ * R rotations cost level + 1 forward transforms in all and two inverse
+ * transforms each; a whole linear transform costs level + 1 forward and two
+ * inverse transforms.
+ *
+ * fhe_ct_hoist_batch          ct [batch][2][n] (any u64 words) -> hoisted
+ *   [batch][1 + level][n]:
+ *     row 0     = the words of fhe_ntt_fwd_batch(c0)
+ *     row 1 + l = the words of fhe_ntt_fwd_batch(d_l),
+ *                 d_l = ((c1 mod q) >> l*base_log) & (2^base_log - 1)
+ *   relinearisation's unsigned digits of c1 ITSELF, not of sigma_g(c1).
+ *   (base_log, level) as fhe_relinearize_batch, and level >= 1 ("at least one
+ *   decomposition level is needed").
+ * fhe_ct_hoisted_galois_batch hoisted -> out [batch][nrot][2][n].  With g =
+ *   gs[r] and (a_l, b_l) key block key_idx ? key_idx[r] : r of swk_ntt
+ *   [nkeys][level][2][n] (the prepared Galois keys of fhe_switch_key_generate,
+ *   unchanged: sum_l sigma_g(d_l) 2^(l base_log) = sigma_g(c1) mod q):
+ *     out0 = sigma_g(c0) + sum_l sigma_g(d_l) (*) b_l
+ *     out1 =               sum_l sigma_g(d_l) (*) a_l
+ *   canonical, coefficient form.  Word-identical to the chain:
+ *   fhe_poly_galois_batch on c0 and on each digit row (sigma_g mod q turns a
+ *   digit d into q - d where it negates), fhe_ntt_fwd_batch,
+ *   fhe_pointwise_batch with fhe_ntt_fwd_batch of the key rows a_l / b_l (the
+ *   prepared rows without their Montgomery factor), fhe_poly_add_batch,
+ *   fhe_ntt_inv_batch.  For g = 1 the words equal fhe_ct_galois_batch(g = 1,
+ *   add_input = 0) exactly.  For g != 1 they DIFFER from fhe_ct_galois_batch,
+ *   whose digits are those of sigma_g(c1) (digits in [0, 2^base_log)), while
+ *   here they are sigma_g of the digits of c1 (in (-2^base_log, 2^base_log)):
+ *   both decrypt to sigma_g of the message with the same noise bound,
+ *   level n (2^base_log - 1) max|e|.  1 <= nrot <= 4096 ("rotations must be
+ *   between 1 and 4096").
+ * fhe_ct_hoisted_linear_batch pts_ntt [nterms][n]: the fhe_ntt_fwd_batch
+ *   words of already-encoded, lifted plaintext polynomials p_r, shared by the
+ *   batch.  out[b] = sum_r p_r (*) (rotation r of ciphertext b as above),
+ *   [batch][2][n]; accumulate != 0 reads out as one more degree-1 term (the
+ *   unrotated diagonal enters this way without a key switch: multiply_plain
+ *   first).  Word-identical to fhe_ct_hoisted_galois_batch, fhe_polymul_batch
+ *   of both components with fhe_ntt_inv_batch(p_r), fhe_ct_sum_batch: every
+ *   step is exact arithmetic on canonical residues.  The plaintext is
+ *   multiplied in once per term, on the spectrum of the bracket, and the sum
+ *   over r runs on spectra.  1 <= nterms <= 4096 ("terms must be between 1 and
+ *   4096").  Noise: terms n (t/2) (input noise + the key-switch bound above).
+ * Common rules.  FHE_MODE_NEGACYCLIC single-device contexts only: a compat or
+ *   a multi-device context answers FHE_ERR_UNSUPPORTED (the compat transform
+ *   does not turn sigma_g into a spectrum permutation), as fhe_simd_ctx_create.
+ *   where: device, or host (every buffer staged, keys and plaintexts included).
+ *   gs / key_idx are HOST arrays in both residences, copied before the call
+ *   returns.  Every g is checked (odd first, then range) and every entry of
+ *   key_idx (below n: a ring of degree n has n Galois elements, no table of
+ *   distinct keys is longer; "key index out of range") before any launch.  The call carries no key count:
+ *   THE CALLER GUARANTEES that swk_ntt holds max(key_idx) + 1 key blocks (nrot /
+ *   nterms blocks with key_idx == NULL); an index beyond the table reads past it.  FHE_ERR_INVALID_ARG: a null
+ *   buffer, batch == 0, a zero or too large count, out overlapping an input
+ *   ("output must not overlap ..."), device buffers not 16-byte aligned; the
+ *   count, null, parity and zero-batch checks come before the context is looked
+ *   at.  Hoisted and plaintext rows are read as canonical words.
+ * Paths.  Two, with bit-identical words and no host synchronisation.  Fused
+ *   kernels (n <= 16384 and q < 2^62 only): the digit extraction inside the
+ *   forward transforms; the gathered key MAC, one workgroup per (ciphertext,
+ *   rotation, component), inside the inverse transform.  Composed: a digit
+ *   kernel and the batched forward transform; a streaming gathered MAC and the
+ *   batched inverse transform in place in the output (the accumulating linear
+ *   transform through a stream-ordered temporary of at most 1 GiB per chunk).
+ *   The fused path is taken where its grid fills the device: the hoist from 256
+ *   ciphertexts, the rotations from batch * nrot >= 4096; the linear transform
+ *   and everything smaller run composed.  FHE_HOIST_FUSED=0 (read per call)
+ *   forces the composed path, FHE_HOIST_FUSED=1 the fused one where it exists. */
+int fhe_ct_hoist_batch(fhe_ctx *ctx, uint32_t base_log, uint32_t level, const uint64_t *ct, uint64_t *hoisted,
+                       size_t batch, int where);
+int fhe_ct_hoisted_galois_batch(fhe_ctx *ctx, uint32_t level, uint32_t nrot, const uint32_t *gs, const uint32_t *key_idx,
+                                const uint64_t *swk_ntt, const uint64_t *hoisted, uint64_t *out, size_t batch, int where);
+int fhe_ct_hoisted_linear_batch(fhe_ctx *ctx, uint32_t level, uint32_t nterms, const uint32_t *gs, const uint32_t *key_idx,
+                                const uint64_t *swk_ntt, const uint64_t *pts_ntt, const uint64_t *hoisted, int accumulate,
+                                uint64_t *out, size_t batch, int where);
+
 /* ---- ciphertext tally (encryption.cpp:1061-1067, 1153-1168, 1327-1460) ---
  * EncryptionEngine::batch_add / batch_add_tree / tally_votes /
  * tally_multi_candidate: the sum of `count` ciphertexts of `polys` (1..3)

@@ -371,4 +371,30 @@ hipError_t launch_simd_permute(const ModConsts &m, uint32_t logn, const uint32_t
                                size_t npoly, hipStream_t s);
 hipError_t launch_simd_lift(uint64_t half, uint64_t lift_add, uint64_t *x, size_t words, hipStream_t s);
 
+// Hoisted Galois key switching (hoist.hip).  hoisted [batch][1 + level][n]:
+// row 0 = fwd(c0), row 1 + l = fwd(d_l), d_l the unsigned digits of c1 mod q.
+// tab [count][2] (device) = (g, key index) per rotation, filled from HOST
+// arrays by launch_hoist_table (key_idx nullable: the identity; the entries
+// travel as kernel arguments, nothing is synchronised).  key [nkeys][level][2][n]
+// prepared (a_l, b_l).  launch_hoist_fwd / launch_hoist_apply: the fused family
+// only (n <= 16384, q < 2^62), level >= 1, count <= kHoistMaxCount.  apply with
+// pts == nullptr: out [batch][count][2][n], rotation r of ciphertext b; with
+// pts [count][n] (canonical spectra): out [batch][2][n] = sum_r p_r (*)
+// rotation r (+ out mod q with accumulate).
+constexpr uint32_t kHoistMaxCount = 4096;
+hipError_t launch_hoist_table(const uint32_t *gs, const uint32_t *key_idx, size_t count, uint32_t *tab, hipStream_t s);
+hipError_t launch_hoist_fwd(const Plan &p, int level, int base_log, const uint64_t *ct, uint64_t *hoisted, size_t batch);
+hipError_t launch_hoist_apply(const Plan &p, int level, const uint32_t *tab, uint32_t count, const uint64_t *key,
+                              const uint64_t *pts, const uint64_t *hoisted, int accumulate, uint64_t *out, size_t batch);
+// Composed path, any n = 2^logn and odd q: the digit rows (row 0 = c0's raw
+// words) for the batched forward transform, and the gathered key MAC into
+// spectra spec [batch][count][2][n] (pts != nullptr: [batch][2][n], summed over
+// the terms) for the batched inverse.  word = the Montgomery word of the
+// prepared keys (32, 64, or 65 for q >= 2^62).
+hipError_t launch_hoist_digits(const ModConsts &m, uint32_t logn, uint32_t base_log, uint32_t level, const uint64_t *ct,
+                               uint64_t *rows, size_t batch, hipStream_t s);
+hipError_t launch_hoist_mac(const ModConsts &m, uint32_t logn, int word, int level, const uint32_t *tab, uint32_t count,
+                            const uint64_t *key, const uint64_t *pts, const uint64_t *hoisted, uint64_t *spec, size_t batch,
+                            hipStream_t s);
+
 }  // namespace FHE_NS

@@ -180,6 +180,12 @@ SIGNATURES = [
     ("fhe_ct_galois_chain_batch", C.c_int,
      [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, C.c_int, vp,
       C.c_size_t, C.c_int]),
+    ("fhe_ct_hoist_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_hoisted_galois_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp, C.c_size_t, C.c_int]),
+    ("fhe_ct_hoisted_linear_batch", C.c_int,
+     [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp, C.c_int, vp, C.c_size_t,
+      C.c_int]),
     ("fhe_glwe_rotate_batch", C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_cmux_batch", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_size_t, C.c_int]),
     ("fhe_blind_rotate_batch", C.c_int,
@@ -896,6 +902,31 @@ class SwitchKey:
         return self._ntt
 
 
+class HoistedCiphertext:
+    """A ciphertext decomposed and transformed once (EncryptionEngine.hoist,
+    fhe_ct_hoist_batch): ``buf`` [..., 1 + level, n] holds the spectrum of c0
+    and of the `level` unsigned base-2^base_log digits of c1.  ``ct`` is the
+    ciphertext it came from (the unrotated term of a linear transform needs
+    it)."""
+
+    def __init__(self, ring: "PolynomialRing", buf, base_log: int, level: int, ct=None):
+        buf = _as_u64(buf)
+        if len(buf.shape) < 2 or tuple(buf.shape[-2:]) != (1 + int(level), ring.degree):
+            raise FHEError(-9, "hoisted buffer must have shape [..., 1 + level, n]")
+        self.ring, self.buf, self.base_log, self.level, self.ct = ring, buf, int(base_log), int(level), ct
+
+
+class PreparedPlaintext:
+    """One plaintext of a linear transform, already encoded and lifted
+    (EncryptionEngine.prepare_plain): ``coeff`` [n] the polynomial (what the
+    unrotated term multiplies by), ``row`` [n] its transform (what the rotated
+    terms multiply by).  Host arrays or device tensors; they stay where they
+    are."""
+
+    def __init__(self, row, coeff):
+        self.row, self.coeff = _as_u64(row), _as_u64(coeff)
+
+
 class SecretKey:
     """SecretKey (key_manager.h): the polynomial s [n] and its NTT-domain
     form prepared once on the GPU (fhe_secret_key_prepare: s and s^2)."""
@@ -1114,13 +1145,28 @@ class KeyGenerator:
         the rows left by 2^i), the last one for g = 2n - 1 (swap the rows) --
         the slot-sum list of include/fhe_gpu.h.  Key i on streams
         stream + 2 level i ..., as galois_keys."""
+        return self._galois_key_set(sk, slot_sum_elements(self.ring.degree), base_log, level, stream)
+
+    def _galois_key_set(self, sk, gs, base_log: int, level: int, stream: int):
+        """One Galois key per element of gs in one buffer [len(gs), level, 2, n],
+        key i on streams stream + 2 level i ...."""
         r = self.ring
         s = _as_u64(sk.poly if isinstance(sk, SecretKey) else sk)
-        gs = slot_sum_elements(r.degree)
         out = _empty(s, (len(gs), level, 2, r.degree))
         for i, g in enumerate(gs):
             self.switch_key(s, s, base_log, level, stream + 2 * level * i, g, out=out[i])
         return SwitchKey(r, out, base_log, level, gs)
+
+    def rotation_keys_for(self, sk, steps, base_log: int, level: int, stream: int, swap_rows: bool = False):
+        """One Galois key per requested row-rotation step in one buffer
+        [len(steps), level, 2, n]: key i for g_i = rotation_element(n, steps[i],
+        swap_rows), on streams stream + 2 level i ....  rotation_keys holds the
+        power-of-two steps only; rotate_many / linear_transform / matvec look a
+        step's key up by its element in the returned SwitchKey's g list."""
+        gs = [rotation_element(self.ring.degree, int(st), swap_rows) for st in steps]
+        if not gs:
+            raise FHEError(-9, "at least one step is needed")
+        return self._galois_key_set(sk, gs, base_log, level, stream)
 
     def threshold_keys(self, threshold: int, total_shares: int, stream: int, device_out: bool = False):
         """generate_threshold_keys (:479-546): a ternary master key from
@@ -2211,6 +2257,150 @@ class EncryptionEngine:
         if ns == 0:
             return self.ring.galois(_as_u64(ct), 1, out)
         return self.galois_chain(ct, list(keys.g[:ns]), keys, None, True, out)
+
+    # ---- hoisted rotations and the plaintext linear transform
+    def hoist(self, ct, base_log: int, level: int, out=None) -> "HoistedCiphertext":
+        """fhe_ct_hoist_batch: decompose and transform ct [..., 2, n] once for
+        any number of rotations with keys of the same (base_log, level)."""
+        r = self.ring
+        ct = _as_u64(ct)
+        nb = _lead(ct, (2, r.degree))
+        if out is None:
+            out = _empty(ct, tuple(ct.shape[:-2]) + (1 + int(level), r.degree))
+        bi, bo = _Buf(ct), _Buf(out, True)
+        if bo.count != nb * (1 + int(level)) * r.degree:
+            raise FHEError(-9, "hoisted buffer must be [..., 1 + level, n]")
+        w = _where(bi, bo)
+        r._bind_stream(w)
+        _check(lib().fhe_ct_hoist_batch(r._h, int(base_log), int(level), bi.ptr, bo.ptr, nb, w))
+        return HoistedCiphertext(r, out, base_log, level, ct)
+
+    def _hoisted_for(self, x, keys: "SwitchKey") -> "HoistedCiphertext":
+        if keys.steps is None:
+            raise FHEError(-9, "needs keys [nkeys, level, 2, n] (KeyGenerator.rotation_keys_for)")
+        if not isinstance(x, HoistedCiphertext):
+            return self.hoist(x, keys.base_log, keys.level)
+        if (x.base_log, x.level) != (keys.base_log, keys.level):
+            raise FHEError(-9, "the hoisted ciphertext and the keys differ in (base_log, level)")
+        return x
+
+    def _step_keys(self, steps, keys: "SwitchKey"):
+        """(gs, key indices) of row-rotation steps in keys.g."""
+        n = self.ring.degree
+        have = {int(g): i for i, g in reversed(list(enumerate(keys.g)))}
+        gs = [rotation_element(n, int(st)) for st in steps]
+        missing = [int(st) for st, g in zip(steps, gs) if g not in have]
+        if missing:
+            raise FHEError(-9, "no key for rotation step(s) %s (KeyGenerator.rotation_keys_for)" % missing)
+        return gs, [have[g] for g in gs]
+
+    def rotate_many(self, ct, steps, keys: "SwitchKey", out=None):
+        """Every row rotation in `steps` of ct (a ciphertext batch or a
+        HoistedCiphertext) in one fhe_ct_hoisted_galois_batch call ->
+        [..., len(steps), 2, n].  One key per step, looked up in keys.g."""
+        r = self.ring
+        h = self._hoisted_for(ct, keys)
+        steps = [int(st) for st in steps]
+        if not steps:
+            raise FHEError(-9, "at least one step is needed")
+        gs, idx = self._step_keys(steps, keys)
+        nb = _lead(h.buf, (1 + h.level, r.degree))
+        if out is None:
+            out = _empty(h.buf, tuple(h.buf.shape[:-2]) + (len(steps), 2, r.degree))
+        bh, bk, bo = _Buf(h.buf), _Buf(keys.key_ntt), _Buf(out, True)
+        if bo.count != nb * len(steps) * 2 * r.degree:
+            raise FHEError(-9, "output must be [..., len(steps), 2, n]")
+        w = _where(bh, bk, bo)
+        r._bind_stream(w)
+        ns = len(steps)
+        _check(lib().fhe_ct_hoisted_galois_batch(r._h, h.level, ns, (C.c_uint32 * ns)(*gs), (C.c_uint32 * ns)(*idx), bk.ptr,
+                                                 bh.ptr, bo.ptr, nb, w))
+        return out
+
+    def prepare_plain(self, values, like=None) -> "PreparedPlaintext":
+        """n slot values -> the plaintext linear_transform multiplies by,
+        encoded with lift=True and transformed; resident where `like` is
+        (a device tensor: on its device), else where `values` are."""
+        return self._prepare_plains([values], like)[0]
+
+    def _prepare_plains(self, values, like=None):
+        """prepare_plain of a list of slot vectors in one encode and one transform."""
+        n = self.ring.degree
+        if all(_is_tensor(v) for v in values):
+            v = torch.stack([x.reshape(n) for x in values])
+        else:
+            v = np.stack([np.asarray(H, dtype=np.uint64).reshape(n) for H in values])
+            if _is_tensor(like):
+                v = torch.from_numpy(v.view(np.int64)).to(like.device)
+        coeff = self.simd.encode(v, True)
+        rows = self.ring.forward_ntt(coeff)
+        return [PreparedPlaintext(rows[i], coeff[i]) for i in range(len(values))]
+
+    def linear_transform(self, ct, diagonals, keys: "SwitchKey", out=None):
+        """sum over the items of `diagonals` {row-rotation step: plaintext} of
+        plaintext (*) rotate(ct, step) -> [..., 2, n], in one
+        fhe_ct_hoisted_linear_batch call: `level + 1` forward and two inverse
+        transforms for the whole sum.  A plaintext is n slot values or a
+        PreparedPlaintext (resident where the ciphertext is).  Step 0 (mod n/2)
+        needs no key: it enters through multiply_plain and `accumulate`."""
+        r = self.ring
+        n = r.degree
+        h = self._hoisted_for(ct, keys)
+        rows, steps, zero = [], [], None
+        items = list(diagonals.items())
+        raw = [i for i, (_, pt) in enumerate(items) if not isinstance(pt, PreparedPlaintext)]
+        if raw:
+            for i, pt in zip(raw, self._prepare_plains([items[i][1] for i in raw], h.buf)):
+                items[i] = (items[i][0], pt)
+        for st, pt in items:
+            if int(st) % (n // 2) == 0:
+                zero = pt.coeff if zero is None else r.add(zero.reshape(1, n), pt.coeff.reshape(1, n))[0]
+            else:
+                rows.append(pt.row)
+                steps.append(int(st))
+        acc = 0
+        if zero is not None:
+            if h.ct is None:
+                raise FHEError(-9, "step 0 needs the ciphertext itself (hoist() keeps it)")
+            out = self.multiply_plain(h.ct, zero, out)
+            acc = 1
+        if not rows:
+            if zero is None:
+                raise FHEError(-9, "at least one diagonal is needed")
+            return out
+        gs, idx = self._step_keys(steps, keys)
+        nb = _lead(h.buf, (1 + h.level, n))
+        if out is None:
+            out = _empty(h.buf, tuple(h.buf.shape[:-2]) + (2, n))
+        pts = torch.stack(rows) if _is_tensor(rows[0]) else np.stack(rows)
+        bh, bk, bp, bo = _Buf(h.buf), _Buf(keys.key_ntt), _Buf(pts), _Buf(out, True)
+        if bo.count != nb * 2 * n:
+            raise FHEError(-9, "output must be [..., 2, n]")
+        w = _where(bh, bk, bp, bo)
+        r._bind_stream(w)
+        nt = len(steps)
+        _check(lib().fhe_ct_hoisted_linear_batch(r._h, h.level, nt, (C.c_uint32 * nt)(*gs), (C.c_uint32 * nt)(*idx), bk.ptr,
+                                                 bp.ptr, bh.ptr, acc, bo.ptr, nb, w))
+        return out
+
+    def matvec(self, ct, M, keys: "SwitchKey", out=None):
+        """M v mod t for a D x D integer matrix M, D a power of two dividing
+        n/2, and ct the encryption of v tiled with period D along both slot
+        rows: diagonal j, diag_j[i] = M[i][(i + j) mod D] tiled, times the
+        rotation by j, summed by linear_transform.  The result holds M v
+        tiled.  `keys` holds the steps 1 .. D - 1 (rotation_keys_for)."""
+        n = self.ring.degree
+        M = np.asarray(M, dtype=object)
+        D = int(M.shape[0]) if M.ndim == 2 else 0
+        if D < 1 or M.shape[1] != D or (D & (D - 1)) or (n // 2) % D:
+            raise FHEError(-9, "the matrix must be D x D with D a power of two dividing n/2")
+        t = self.t or 4
+        i = np.arange(D)
+        diags = {}
+        for j in range(D):
+            d = np.array([int(M[a, (a + j) % D]) % t for a in i], dtype=np.uint64)
+            diags[j] = np.tile(d, n // D)
+        return self.linear_transform(ct, diags, keys, out)
 
     def inner_product_scaled(self, ct1, ct2, ek: EvaluationKey, keys: "SwitchKey", out=None):
         """<v, w> mod t in every slot of SIMD-encoded encryptions of v and w:

@@ -407,6 +407,27 @@ export interface FHESimdEngine extends FHEScaledEngine {
   innerProductScaled(ct1: Ciphertext, ct2: Ciphertext, ek: EvaluationKey, keys: RotationKeys): Promise<Ciphertext>;
 }
 
+/** A ciphertext decomposed and transformed once (FHEHoistEngine.hoist) for any number of rotations */
+export interface HoistedCiphertext {
+  readonly __brand: 'HoistedCiphertext';
+  readonly handle: bigint;
+  readonly keyId: bigint;
+  readonly noiseBudget: number;
+  readonly decompBaseLog: number;
+  readonly decompLevel: number;
+}
+
+/** Hoisted rotations and the plaintext linear transform (fhe_ct_hoist_batch,
+ * fhe_ct_hoisted_galois_batch, fhe_ct_hoisted_linear_batch): many rotations of one ciphertext
+ * share one decomposition and level + 1 forward transforms; linearTransform sums
+ * values (*) rotate(ct, step) over its entries with two inverse transforms in all. */
+export interface FHEHoistEngine extends FHESimdEngine {
+  generateRotationKeysFor(sk: SecretKey, steps: number[], options?: PackKeyOptions): Promise<RotationKeys>;
+  hoist(ct: Ciphertext, keys: RotationKeys): Promise<HoistedCiphertext>;
+  rotateMany(ct: Ciphertext | HoistedCiphertext, steps: number[], keys: RotationKeys): Promise<Ciphertext[]>;
+  linearTransform(ct: Ciphertext | HoistedCiphertext, diagonals: Map<number, bigint[]> | Array<[number, bigint[]]>, keys: RotationKeys): Promise<Ciphertext>;
+}
+
 /** Options of this backend (environment defaults FHE_NTT_MODE, FHE_GPU_DEVICES). */
 export interface EngineOptions {
   mode?: 'compat' | 'negacyclic';
@@ -495,6 +516,10 @@ export declare class FHEEngineImpl implements FHETallyEngine {
   rotateColumns(ct: Ciphertext, keys: RotationKeys): Promise<Ciphertext>;
   sumSlots(ct: Ciphertext, keys: RotationKeys, options?: { rowsOnly?: boolean }): Promise<Ciphertext>;
   innerProductScaled(ct1: Ciphertext, ct2: Ciphertext, ek: EvaluationKey, keys: RotationKeys): Promise<Ciphertext>;
+  generateRotationKeysFor(sk: SecretKey, steps: number[], options?: PackKeyOptions): Promise<RotationKeys>;
+  hoist(ct: Ciphertext, keys: RotationKeys): Promise<HoistedCiphertext>;
+  rotateMany(ct: Ciphertext | HoistedCiphertext, steps: number[], keys: RotationKeys): Promise<Ciphertext[]>;
+  linearTransform(ct: Ciphertext | HoistedCiphertext, diagonals: Map<number, bigint[]> | Array<[number, bigint[]]>, keys: RotationKeys): Promise<Ciphertext>;
   /** The device buffer behind a handle (this backend's extension); part names another
    * native buffer of the handle (a bootstrap key's 'kskA' / 'kskB'). */
   deviceBuffer(handle: unknown, part?: string): DeviceBuffer | undefined;
@@ -646,6 +671,15 @@ export declare class NttContext {
   /** fhe_ct_galois_chain_batch: x <- ctGalois(gs[i], key keyIdx[i] of keysPrep, x, addInput) for every i */
   ctGaloisChain(baseLog: number, level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ct: Words, addInput: number, out: Words): Words;
   ctGaloisChainAsync(baseLog: number, level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ct: Words, addInput: number, out: Words): Promise<Words>;
+  /** fhe_ct_hoist_batch: ct [batch][2][n] -> out [batch][1 + level][n], the spectra of c0 and of the digits of c1 */
+  ctHoist(baseLog: number, level: number, ct: Words, out: Words): Words;
+  ctHoistAsync(baseLog: number, level: number, ct: Words, out: Words): Promise<Words>;
+  /** fhe_ct_hoisted_galois_batch: out [batch][gs.length][2][n], rotation gs[r] with key keyIdx[r] of keysPrep */
+  ctHoistedGalois(level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, hoisted: Words, out: Words): Words;
+  ctHoistedGaloisAsync(level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, hoisted: Words, out: Words): Promise<Words>;
+  /** fhe_ct_hoisted_linear_batch: out [batch][2][n] = sum_r ptsNtt[r] (*) rotation r (+ out when accumulate) */
+  ctHoistedLinear(level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ptsNtt: Words, hoisted: Words, accumulate: number, out: Words): Words;
+  ctHoistedLinearAsync(level: number, gs: BigUint64Array, keyIdx: BigUint64Array, keysPrep: Words, ptsNtt: Words, hoisted: Words, accumulate: number, out: Words): Promise<Words>;
   /** Scale-invariant products round(t/q (ct1 (x) ct2)) (t: plaintext modulus, 0 selects 4); the
    * context keeps one scale context per t.  ct [batch][2][n] -> out [batch][3][n] */
   ctMultiplyScaled(t: bigint | number, ct1: Words, ct2: Words, out: Words): Words;

@@ -1485,6 +1485,7 @@ function makeEngineClass(native) {
       if (this._mode !== 1) throw new FHEError('slot rotations need mode negacyclic', FHEErrorCode.INVALID_PARAMETERS);
       if (a.comps !== 2 || ct.isNtt) throw new FHEError('slot rotations take degree-1 coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
       if (ct.keyId !== keys.keyId) throw new FHEError('Rotation keys do not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+      if (k.forSteps) throw new FHEError('these keys hold explicit steps: use rotateMany / linearTransform', FHEErrorCode.INVALID_PARAMETERS);
       const out = this._buf(2 * n);
       if (idx.length === 0) {
         await this._ctx.polyGaloisAsync(a.buf, 1, out);
@@ -1523,6 +1524,118 @@ function makeEngineClass(native) {
     async innerProductScaled(ct1, ct2, ek, keys) {
       const prod = await this.relinearize(await this.multiplyScaled(ct1, ct2), ek);
       return this.sumSlots(prod, keys);
+    }
+
+    // ---- hoisted rotations and the plaintext linear transform (fhe_ct_hoist_batch,
+    // fhe_ct_hoisted_galois_batch, fhe_ct_hoisted_linear_batch): a ciphertext is decomposed and
+    // transformed once, every rotation of it is then a gathered key product on the spectra.
+    /** 3^(steps mod n/2) mod 2n: the Galois element of a row rotation by `steps` */
+    _rotationElement(steps) {
+      if (!Number.isInteger(steps)) throw new FHEError('steps must be integers', FHEErrorCode.INVALID_PARAMETERS);
+      const half = this._n / 2, two = BigInt(2 * this._n);
+      let m = ((steps % half) + half) % half, g = 1n, b = 3n;
+      for (; m; m = Math.floor(m / 2)) { if (m & 1) g = (g * b) % two; b = (b * b) % two; }
+      return Number(g);
+    }
+    /** One Galois key per requested row-rotation step (generateRotationKeys holds the
+     *  power-of-two steps only): the keys of rotateMany / linearTransform */
+    async generateRotationKeysFor(sk, steps, options) {
+      this._check();
+      return guard(async () => {
+        const s = this._st(sk, 'SecretKey');
+        if (!Array.isArray(steps) || steps.length === 0) throw new FHEError('expected a list of steps', FHEErrorCode.INVALID_PARAMETERS);
+        const n = this._n, gs = steps.map((st) => this._rotationElement(st));
+        const { bl, lv } = this._switchDecomp(options);
+        const per = lv * 2 * n;
+        const raw = this._buf(gs.length * per), prep = this._buf(gs.length * per);
+        for (let i = 0; i < gs.length; i++) await this._switchKeyInto(s, s, gs[i], bl, lv, raw.view(i * per, per));
+        await this._ctx.prepareRelinKeyAsync(raw, prep);
+        raw.free();
+        return this._handle('RotationKeys', { keyId: sk.keyId, steps: gs.length, decompBaseLog: bl, decompLevel: lv },
+          { buf: prep, baseLog: bl, level: lv, gs, forSteps: true });
+      });
+    }
+    _stepKeys(steps, k) {
+      const gs = steps.map((st) => this._rotationElement(st));
+      const idx = gs.map((g) => k.gs.indexOf(g));
+      if (idx.some((i) => i < 0)) throw new FHEError('no key for a requested rotation step (generateRotationKeysFor)', FHEErrorCode.INVALID_PARAMETERS);
+      return { gs: BigUint64Array.from(gs, (g) => BigInt(g)), idx: BigUint64Array.from(idx, (i) => BigInt(i)) };
+    }
+    async _hoisted(x, k, keys) {
+      if (x && x.__brand === 'HoistedCiphertext') {
+        const h = this._st(x, 'HoistedCiphertext');
+        if (h.baseLog !== k.baseLog || h.level !== k.level) throw new FHEError('the hoisted ciphertext and the keys differ in their decomposition', FHEErrorCode.INVALID_PARAMETERS);
+        if (x.keyId !== keys.keyId) throw new FHEError('Rotation keys do not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+        return h;
+      }
+      return this._st(await this.hoist(x, keys), 'HoistedCiphertext');
+    }
+    /** Decompose and transform a degree-1 ciphertext once for any number of rotations with `keys` */
+    async hoist(ct, keys) {
+      this._check();
+      return guard(async () => {
+        const a = this._rlwe(ct), k = this._st(keys, 'RotationKeys'), n = this._n;
+        if (this._mode !== 1) throw new FHEError('slot rotations need mode negacyclic', FHEErrorCode.INVALID_PARAMETERS);
+        if (a.comps !== 2 || ct.isNtt) throw new FHEError('slot rotations take degree-1 coefficient-form ciphertexts', FHEErrorCode.INVALID_PARAMETERS);
+        if (ct.keyId !== keys.keyId) throw new FHEError('Rotation keys do not match the ciphertext key', FHEErrorCode.KEY_MISMATCH);
+        const buf = this._buf((1 + k.level) * n);
+        await this._ctx.ctHoistAsync(k.baseLog, k.level, a.buf, buf);
+        return this._handle('HoistedCiphertext', { keyId: ct.keyId, noiseBudget: ct.noiseBudget, decompBaseLog: k.baseLog, decompLevel: k.level },
+          { buf, ct: a.buf, baseLog: k.baseLog, level: k.level });
+      });
+    }
+    /** Every row rotation in `steps` of one ciphertext (or hoisted ciphertext) in one call */
+    async rotateMany(ct, steps, keys) {
+      this._check();
+      return guard(async () => {
+        const k = this._st(keys, 'RotationKeys'), n = this._n;
+        if (!Array.isArray(steps) || steps.length === 0) throw new FHEError('expected a list of steps', FHEErrorCode.INVALID_PARAMETERS);
+        const h = await this._hoisted(ct, k, keys), t = this._stepKeys(steps, k);
+        const all = this._buf(steps.length * 2 * n);
+        await this._ctx.ctHoistedGaloisAsync(k.level, t.gs, t.idx, k.buf, h.buf, all);
+        const out = steps.map((_, i) => this._ct(this._buf(2 * n).copyFrom(all, 0, i * 2 * n, 2 * n), ct.keyId, ct.noiseBudget - 1, 1, { packed: true }));
+        all.free();
+        return out;
+      });
+    }
+    /** sum over the entries [step, slot values] of `diagonals` of values (*) rotate(ct, step):
+     *  one hoisted call, level + 1 forward and two inverse transforms for the whole sum.  Step 0
+     *  (mod n/2) needs no key: it enters as a plaintext product. */
+    async linearTransform(ct, diagonals, keys) {
+      this._check();
+      return guard(async () => {
+        const k = this._st(keys, 'RotationKeys'), n = this._n, half = n / 2;
+        const entries = diagonals instanceof Map ? Array.from(diagonals.entries()) : diagonals;
+        if (!Array.isArray(entries) || entries.length === 0) throw new FHEError('expected [step, values] entries', FHEErrorCode.INVALID_PARAMETERS);
+        const h = await this._hoisted(ct, k, keys);
+        const out = this._buf(2 * n), steps = [], rows = [];
+        let acc = 0;
+        for (const [st, values] of entries) {
+          const src = this._upload(this._simdWords(values)), enc = this._buf(n);
+          await this._ctx.simdEncodeAsync(this._tEff, src, 1, enc);
+          src.free();
+          if (((st % half) + half) % half === 0) {
+            if (acc) throw new FHEError('step 0 given twice', FHEErrorCode.INVALID_PARAMETERS);
+            const rep = this._buf(2 * n).copyFrom(enc, 0, 0, n).copyFrom(enc, n, 0, n);
+            await this._ctx.polymulAsync(h.ct, rep, out);
+            rep.free();
+            enc.free();
+            acc = 1;
+          } else {
+            steps.push(st);
+            rows.push(enc);
+          }
+        }
+        if (rows.length) {
+          const t = this._stepKeys(steps, k), pts = this._buf(rows.length * n);
+          rows.forEach((r, i) => { pts.copyFrom(r, i * n, 0, n); r.free(); });
+          await this._ctx.forwardAsync(pts, pts);
+          await this._ctx.ctHoistedLinearAsync(k.level, t.gs, t.idx, k.buf, pts, h.buf, acc, out);
+          pts.free();
+        }
+        const budget = (ct.noiseBudget === undefined ? 0 : ct.noiseBudget) - 3;
+        return this._ct(out, ct.keyId, budget, 1, { packed: true });
+      });
     }
 
     // ---- serialisation: binary = header words + the native words, checksum = SHA-256

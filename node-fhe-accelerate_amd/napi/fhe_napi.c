@@ -1965,6 +1965,103 @@ static napi_value ctx_ct_galois_chain(napi_env env, napi_callback_info info) {
     return job_go(env, &k, j, k.argv[7], keep, 3);
 }
 
+/* ---- hoisted rotations (fhe_ct_hoist_batch, fhe_ct_hoisted_galois_batch, fhe_ct_hoisted_linear_batch) */
+/* ctHoist(baseLog, level, ct [batch][2][n], out [batch][1 + level][n]) */
+static int run_ct_hoist(job *j) {
+    return fhe_ct_hoist_batch(j->c, (uint32_t)j->v[0], (uint32_t)j->v[1], j->p[0], j->p[1], j->batch, j->where);
+}
+static napi_value ctx_ct_hoist(napi_env env, napi_callback_info info) {
+    call k;
+    if (call_begin(env, info, 4, &k)) return NULL;
+    uint64_t bl, lv, *ct, *o;
+    size_t nc, no;
+    if (num_arg(env, &k, 0, &bl) || num_arg(env, &k, 1, &lv) || arr_arg(env, &k, 2, &ct, &nc) || arr_arg(env, &k, 3, &o, &no) ||
+        lv == 0 || lv > 64)
+        return bad_args(env, "ctHoist(baseLog, level, ct [batch*2n], out [batch*(1+level)*n])"), NULL;
+    if (nc == 0 || nc % (2 * k.n) || no != nc / 2 * (1 + lv)) return range_err(env, "ct [batch][2][n], out [batch][1+level][n]");
+    job *j = job_new(&k, run_ct_hoist, NULL);
+    j->p[0] = ct; j->p[1] = o; j->v[0] = bl; j->v[1] = lv; j->batch = nc / (2 * k.n);
+    napi_value keep[2] = {k.argv[2], k.argv[3]};
+    return job_go(env, &k, j, k.argv[3], keep, 2);
+}
+/* the (g, key index) lists of a hoisted call as one owned uint32 block: 0, or 1 when an element or
+ * an index is out of range (both must fit 32 bits; the index must lie inside keysPrep), 2 without memory */
+static int hoist_lists(const uint64_t *gs, const uint64_t *ki, size_t ng, size_t per, size_t nk, uint64_t **out) {
+    for (size_t i = 0; i < ng; ++i)
+        if (gs[i] >> 32 || ki[i] >> 32 || (ki[i] + 1) * per > nk) return 1;
+    uint32_t *t = (uint32_t *)malloc(2 * ng * 4 + 8);
+    if (!t) return 2;
+    for (size_t i = 0; i < ng; ++i) {
+        t[i] = (uint32_t)gs[i];
+        t[ng + i] = (uint32_t)ki[i];
+    }
+    *out = (uint64_t *)t;
+    return 0;
+}
+/* ctHoistedGalois(level, gs, keyIdx (host BigUint64Arrays [nrot]), keysPrep [nkeys][level][2][n],
+ * hoisted [batch][1 + level][n], out [batch][nrot][2][n]) */
+static int run_ct_hoisted_galois(job *j) {
+    const uint32_t ns = (uint32_t)j->v[1], *g = (const uint32_t *)j->owned;
+    return fhe_ct_hoisted_galois_batch(j->c, (uint32_t)j->v[0], ns, g, g + ns, j->p[0], j->p[1], j->p[2], j->batch, j->where);
+}
+static napi_value ctx_ct_hoisted_galois(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "ctHoistedGalois(level, gs (BigUint64Array), keyIdx (BigUint64Array), keysPrep [nkeys*level*2n], "
+        "hoisted [batch*(1+level)*n], out [batch*nrot*2n])";
+    call k;
+    if (call_begin(env, info, 6, &k)) return NULL;
+    uint64_t lv, *gs, *ki, *key, *h, *o;
+    size_t ng, nki, nk, nh, no;
+    if (num_arg(env, &k, 0, &lv) || k.argc < 3 || get_u64_array(env, k.argv[1], &gs, &ng) ||
+        get_u64_array(env, k.argv[2], &ki, &nki) || arr_arg(env, &k, 3, &key, &nk) || arr_arg(env, &k, 4, &h, &nh) ||
+        arr_arg(env, &k, 5, &o, &no) || ng == 0 || ng > 4096 || nki != ng || lv == 0 || lv > 64)
+        return bad_args(env, usage), NULL;
+    const size_t hp = (1 + lv) * k.n;
+    if (nh == 0 || nh % hp || no != nh / hp * ng * 2 * k.n) return range_err(env, "hoisted [batch][1+level][n], out [batch][nrot][2][n]");
+    uint64_t *lists = NULL;
+    const int lrc = hoist_lists(gs, ki, ng, lv * 2 * k.n, nk, &lists);
+    if (lrc) return range_err(env, lrc == 1 ? "Galois element or key index out of range" : "out of memory");
+    job *j = job_new(&k, run_ct_hoisted_galois, NULL);
+    j->owned = lists;
+    j->p[0] = key; j->p[1] = h; j->p[2] = o;
+    j->v[0] = lv; j->v[1] = ng; j->batch = nh / hp;
+    napi_value keep[3] = {k.argv[3], k.argv[4], k.argv[5]};
+    return job_go(env, &k, j, k.argv[5], keep, 3);
+}
+/* ctHoistedLinear(level, gs, keyIdx, keysPrep, ptsNtt [nterms][n], hoisted, accumulate, out [batch][2][n]):
+ * out = sum_r ptsNtt[r] (*) rotation r (+ out) */
+static int run_ct_hoisted_linear(job *j) {
+    const uint32_t ns = (uint32_t)j->v[1], *g = (const uint32_t *)j->owned;
+    return fhe_ct_hoisted_linear_batch(j->c, (uint32_t)j->v[0], ns, g, g + ns, j->p[0], j->p[1], j->p[2], (int)j->v[2], j->p[3],
+                                       j->batch, j->where);
+}
+static napi_value ctx_ct_hoisted_linear(napi_env env, napi_callback_info info) {
+    static const char *usage =
+        "ctHoistedLinear(level, gs (BigUint64Array), keyIdx (BigUint64Array), keysPrep [nkeys*level*2n], "
+        "ptsNtt [nterms*n], hoisted [batch*(1+level)*n], accumulate, out [batch*2n])";
+    call k;
+    if (call_begin(env, info, 8, &k)) return NULL;
+    uint64_t lv, *gs, *ki, *key, *pt, *h, acc, *o;
+    size_t ng, nki, nk, np, nh, no;
+    if (num_arg(env, &k, 0, &lv) || k.argc < 3 || get_u64_array(env, k.argv[1], &gs, &ng) ||
+        get_u64_array(env, k.argv[2], &ki, &nki) || arr_arg(env, &k, 3, &key, &nk) || arr_arg(env, &k, 4, &pt, &np) ||
+        arr_arg(env, &k, 5, &h, &nh) || num_arg(env, &k, 6, &acc) || arr_arg(env, &k, 7, &o, &no) || ng == 0 || ng > 4096 ||
+        nki != ng || lv == 0 || lv > 64)
+        return bad_args(env, usage), NULL;
+    const size_t hp = (1 + lv) * k.n;
+    if (nh == 0 || nh % hp || no != nh / hp * 2 * k.n || np != ng * k.n)
+        return range_err(env, "ptsNtt [nterms][n], hoisted [batch][1+level][n], out [batch][2][n]");
+    uint64_t *lists = NULL;
+    const int lrc = hoist_lists(gs, ki, ng, lv * 2 * k.n, nk, &lists);
+    if (lrc) return range_err(env, lrc == 1 ? "Galois element or key index out of range" : "out of memory");
+    job *j = job_new(&k, run_ct_hoisted_linear, NULL);
+    j->owned = lists;
+    j->p[0] = key; j->p[1] = pt; j->p[2] = h; j->p[3] = o;
+    j->v[0] = lv; j->v[1] = ng; j->v[2] = acc ? 1 : 0; j->batch = nh / hp;
+    napi_value keep[4] = {k.argv[3], k.argv[4], k.argv[5], k.argv[7]};
+    return job_go(env, &k, j, k.argv[7], keep, 4);
+}
+
 /* ---- randomness and key material (fhe_sample_batch, fhe_*_generate) ---- */
 /* sample(kind, seed, stream, noiseStd, out) */
 static int run_sample(job *j) {
@@ -2269,6 +2366,9 @@ static napi_value init(napi_env env, napi_value exports) {
         M("simdEncode", ctx_simd_encode),
         M("simdDecode", ctx_simd_decode),
         M("ctGaloisChain", ctx_ct_galois_chain),
+        M("ctHoist", ctx_ct_hoist),
+        M("ctHoistedGalois", ctx_ct_hoisted_galois),
+        M("ctHoistedLinear", ctx_ct_hoisted_linear),
         M("switchKeyGenerate", ctx_swk_gen),
         M("sample", ctx_sample),
         M("publicKeyGenerate", ctx_pk_gen),
